@@ -16,6 +16,13 @@ Multi-GPU: stripes are independent; each rank owns its own
 batch (weak scaling), RCCL is used only for the start/stop barrier and the
 result allgather.  Inputs are synthetic seeded uniform bytes resident in
 HBM before the timed region.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps steps, print the result line.  --full adds the legs that
+take runs of their own (today the CPU baseline, `cpu_baseline` in the
+result line; null without --full).  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy so two builds can be compared
+output for output (same arguments -> same seeded inputs).
 """
 import argparse
 import json
@@ -61,8 +68,87 @@ def parse_args():
                         "fused compute, framed images stream back D2H "
                         "(BASELINE config 4's 'end-to-end incl. H2D' "
                         "figure; PCIe-bound by design, never `value`)")
-    p.add_argument("--skip-cpu-baseline", action="store_true")
+    p.add_argument("--skip-cpu-baseline", action="store_true",
+                   help="with --full: leave the CPU baseline leg out")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: "
+                        "the CPU baseline leg (cpu_baseline in the result "
+                        "line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step "
+                        "computed to DIR/<name>.npy (rank 0's arrays; "
+                        "float32 samples + float64 checksums, < 64 MB)")
     return p.parse_args()
+
+
+# --dump-outputs budget: every .npy together stays under 64 MB
+DUMP_SAMPLE = 12 << 20   # sampled bytes over all arrays (x4 as float32)
+DUMP_SEG = 64 << 10      # bytes per sampled column segment
+DUMP_ROWS = 1 << 16      # entries per checksum / flag array
+
+
+def _dump_sample(x, budget, rng):
+    """Fixed seeded sample of a 2-D uint8 tensor as float32: everything
+    when it fits the budget, else seeded rows (first and last always) x
+    the head, the tail and one seeded middle segment of each row."""
+    import numpy as np
+    import torch
+    rows, cols = x.shape
+    if rows * cols <= budget:
+        return x.cpu().numpy().astype(np.float32)
+    ci = np.arange(cols)
+    if cols > 3 * DUMP_SEG:
+        mid = int(rng.integers(DUMP_SEG, cols - 2 * DUMP_SEG + 1))
+        ci = np.concatenate([ci[:DUMP_SEG], ci[mid:mid + DUMP_SEG],
+                             ci[cols - DUMP_SEG:]])
+    nr = max(2, budget // len(ci))
+    ri = np.arange(rows)
+    if nr < rows:
+        ri = np.sort(np.concatenate([
+            [0, rows - 1],
+            1 + rng.choice(rows - 2, nr - 2, replace=False)]))
+    sub = x[torch.from_numpy(ri).to(x.device)]
+    sub = sub[:, torch.from_numpy(ci).to(x.device)]
+    return sub.cpu().numpy().astype(np.float32)
+
+
+def _dump_rowsum(x):
+    """Byte sum of every row of a 2-D uint8 tensor (exact in float64), so
+    every output byte reaches the dump; rows are summed in consecutive
+    groups when there are more than DUMP_ROWS of them."""
+    import numpy as np
+    import torch
+    rows = x.shape[0]
+    # torch widens the chunk to int64 before reducing: keep chunks small
+    step = max(1, (512 << 20) // max(1, x.shape[1]))
+    sums = torch.cat([x[lo:lo + step].sum(dim=1, dtype=torch.int64)
+                      for lo in range(0, rows, step)]).cpu().numpy()
+    grp = -(-rows // DUMP_ROWS)
+    if grp > 1:
+        sums = np.concatenate([sums, np.zeros(-rows % grp, np.int64)])
+        sums = sums.reshape(-1, grp).sum(axis=1)
+    return sums.astype(np.float64)
+
+
+def dump_outputs(dirname, tensors, flags):
+    """tensors: {name: 2-D uint8 tensor}; flags: {name: per-row list the
+    timed call returned}.  Writes <name>.npy (seeded sample),
+    <name>_rowsum.npy, and for flags the first DUMP_ROWS entries plus
+    <name>_nonzero.npy (how many entries of the whole list are set, i.e.
+    not 0 / not -1 for a first-bad-block list)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(0xD0D0)
+    budget = DUMP_SAMPLE // max(1, len(tensors))
+    for name, x in tensors.items():
+        np.save(os.path.join(dirname, name + ".npy"),
+                _dump_sample(x, budget, rng))
+        np.save(os.path.join(dirname, name + "_rowsum.npy"), _dump_rowsum(x))
+    for name, (vals, clean) in flags.items():
+        v = np.asarray(vals, dtype=np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), v[:DUMP_ROWS])
+        np.save(os.path.join(dirname, name + "_nonzero.npy"),
+                np.array([np.count_nonzero(v != clean)], dtype=np.float64))
 
 
 def hbm_traffic_lookup(workload):
@@ -176,7 +262,9 @@ def run_host_streamed(args, t, S, ns, enc, rank, world, d):
     enc_sz = crc32block.encode_size(S)
     host_src = torch.empty((B, t.N, S), dtype=torch.uint8,
                            pin_memory=True)
-    host_src.random_(0, 256)
+    hg = torch.Generator()
+    hg.manual_seed(0xB10B5703 ^ rank)
+    host_src.random_(0, 256, generator=hg)
     host_out = torch.empty((2, B * t.total, enc_sz), dtype=torch.uint8,
                            pin_memory=True)
     dev_in = [torch.empty((B, t.total, S), dtype=torch.uint8, device="cuda")
@@ -234,6 +322,9 @@ def run_host_streamed(args, t, S, ns, enc, rank, world, d):
         te = torch.tensor([el], device=tdev)
         td.all_reduce(te, op=td.ReduceOp.MAX)
         el = float(te.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     {"framed_host": host_out.view(-1, enc_sz)}, {})
     src_b = t.N * S * B * nbatches * args.steps * world
     if rank == 0:
         print(json.dumps({
@@ -377,6 +468,8 @@ def main():
         else:
             ev.record()
 
+    last = {}  # what the timed calls of the latest step returned
+
     def step(events=None):
         if events:
             _record(events[0])
@@ -392,7 +485,8 @@ def main():
             if with_crc:
                 codec.encode_batch(framed, flat)
         elif args.workload == "repair":
-            enc.repair_batch(batch, bad, imgs, rbids, rvuids)
+            last["verify_fail"] = enc.repair_batch(batch, bad, imgs, rbids,
+                                                   rvuids)
             if events:
                 _record(events[1])
         else:
@@ -407,7 +501,8 @@ def main():
                 # blocks until the verify stream drains; the trailing
                 # event on the rebuild stream then closes the window over
                 # BOTH overlapped legs (max of the two streams' ends)
-                codec.verify_batch(framed[:, :enc_sz])
+                last["crc_bad_block"] = codec.verify_batch(
+                    framed[:, :enc_sz])
             if events:
                 _record(events[1])
 
@@ -434,6 +529,27 @@ def main():
         te = torch.tensor([elapsed], device=tdev)
         td.all_reduce(te, op=td.ReduceOp.MAX)
         elapsed = float(te.item())
+
+    if args.dump_outputs and rank == 0:
+        # the arrays a caller of the timed path receives (pad bytes of the
+        # framed stride are not output)
+        if fused:
+            outs = {"framed": framed[:, :enc_sz]}
+        elif args.workload == "encode":
+            outs = {"parity%d" % j: batch[:, t.N + j]
+                    for j in range(t.M + t.L)}
+            if with_crc:
+                outs["framed"] = framed[:, :enc_sz]
+        elif args.workload == "repair":
+            outs = {"disk_images": imgs}
+        else:
+            outs = {"rebuilt%d" % i: batch[:, i] for i in bad}
+        flags = {}
+        if "verify_fail" in last:
+            flags["verify_fail"] = (last["verify_fail"], 0)
+        if "crc_bad_block" in last:
+            flags["crc_bad_block"] = (last["crc_bad_block"], -1)
+        dump_outputs(args.dump_outputs, outs, flags)
 
     enc_ms = [a.elapsed_time(b) for a, b in evs]
     rec = {"rank": rank, "stripes": ns, "src_bytes": t.N * S * ns * args.steps}
@@ -483,7 +599,7 @@ def main():
         achieved = alg_bytes / avg_enc_s
         traffic = hbm_traffic_lookup(workload)
         cpu_base = None
-        if (not args.skip_cpu_baseline and world == 1
+        if (args.full and not args.skip_cpu_baseline and world == 1
                 and args.workload == "encode"):
             cpu_base = cpu_baseline_leg(t, S, args.cpu_sample_stripes, with_crc)
         out = {
