@@ -262,7 +262,10 @@ __global__ __launch_bounds__(RS_BLOCK) void rs_apply_k(
       const size_t sub = lane_b / padded;
       stripe = tile * spb + sub;
       off = lane_b - sub * padded;
-      if (stripe >= nstripes) continue;
+      /* lanes past spb*padded (4096 is rarely a multiple of padded) would
+       * land on the NEXT tile's first stripe: redundant today, a double
+       * accumulate under xor_acc */
+      if (sub >= spb || stripe >= nstripes) continue;
     } else {
       stripe = tile / tiles_per_shard;
       off = (tile - stripe * tiles_per_shard) * size_t(RS_TILE) +
@@ -350,7 +353,11 @@ __global__ __launch_bounds__(RS_BLOCK) void rs_apply_k(
       }
     }
     if (VERIFY || cmp_mask) {
-      if (__ballot(mismatch) != 0) {
+      if (spb > 1) {
+        /* a wave spans several packed stripes: lane 0's stripe is not the
+         * mismatching lane's, so every lane reports its own */
+        if (mismatch) atomicOr(&fail[stripe], 1u);
+      } else if (__ballot(mismatch) != 0) {
         if ((threadIdx.x & 63) == 0) atomicOr(&fail[stripe], 1u);
       }
     }

@@ -15,6 +15,25 @@
  * (GFRS_MEM_HOST, staged through pinned buffers internally — the cgo path).
  * A context is thread-safe and may be shared, like one ec.Encoder shared by
  * many goroutines (encoder.go:114-151).
+ *
+ * Layout contract (every entry point; pinned by tests/test_gpu_layout.py):
+ *  - Sources need NO alignment: shard pointers, batch `base`, `src` and
+ *    framed/image inputs may sit at any byte address, shard_len may be any
+ *    positive length (so later shards of a stripe start misaligned), and
+ *    stripe_stride / src_stride / input image strides may carry any
+ *    padding beyond the packed size.  Alignment only affects speed.
+ *  - Destination image rows (framed, dst, disk_dst) are 4-byte aligned:
+ *    the base pointer and framed_stride / dst_stride are multiples of 4;
+ *    the stride may be tight (the image size rounded up to 4) or padded.
+ *    Shards written in place inside `base` (parity, reconstructed shards)
+ *    follow the source rule: no alignment.
+ *  - Only declared outputs are written.  Padding between stripes, between
+ *    image rows and past the last row, and every input shard, are never
+ *    written.  gfrs_encode_frame_batch returning GFRS_ERR_UNSUPPORTED
+ *    writes nothing; when it runs as the encode_batch +
+ *    crc32b_encode_batch composition the parity shards inside `base` are
+ *    written too (encode_batch's declared output), the fused paths leave
+ *    them untouched.
  */
 #ifndef GFRS_H
 #define GFRS_H
