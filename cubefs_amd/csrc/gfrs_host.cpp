@@ -241,6 +241,11 @@ struct gfrs_ctx_impl {
     return GFRS_OK;
   }
 
+  /* gfrs_shard_write_batch returns with its id upload still queued; the
+   * next call must not refill the pinned staging before that copy ran */
+  hipEvent_t ids_ev = nullptr;
+  bool ids_pending = false;
+
   /* stream-lane pool for concurrent foreground (single-stripe) calls;
    * empty when GFRS_LANES=0 or after gfrs_set_stream pins a caller
    * stream (user_stream) */
@@ -263,6 +268,7 @@ struct gfrs_ctx_impl {
     for (int i = 0; i < 2; i++)
       if (aux_ev[i]) hipEventDestroy(aux_ev[i]);
     if (aux_done) hipEventDestroy(aux_done);
+    if (ids_ev) hipEventDestroy(ids_ev);
   }
 };
 
@@ -1234,6 +1240,15 @@ int gfrs_shard_write_batch(gfrs_ctx *ctx, void *dst, size_t dst_stride,
    * (shard.go:241-261) on device - host-side construction was the
    * bottleneck at millions of shards per call */
   const size_t idbytes = size_t(nshards) * 8;
+  /* this call is async, so the previous call's upload may not have read
+   * the staging yet (the legacy repair path issues one call per lost
+   * column back to back: column b then got column b+1's ids) */
+  if (c->ids_pending) {
+    HIP_TRY(hipEventSynchronize(c->ids_ev));
+    c->ids_pending = false;
+  }
+  if (!c->ids_ev)
+    HIP_TRY(hipEventCreateWithFlags(&c->ids_ev, hipEventDisableTiming));
   if ((rc = c->stage_pin.ensure(idbytes * 2)) != GFRS_OK) return rc;
   memcpy(c->stage_pin.p, bids, idbytes);
   memcpy((uint8_t *)c->stage_pin.p + idbytes, vuids, idbytes);
@@ -1241,6 +1256,8 @@ int gfrs_shard_write_batch(gfrs_ctx *ctx, void *dst, size_t dst_stride,
   if ((rc = hbuf.ensure(idbytes * 2)) != GFRS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(hbuf.p, c->stage_pin.p, idbytes * 2,
                          hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->ids_ev, c->stream));
+  c->ids_pending = true;
   /* framed body at +32 */
   launch_crc_encode((uint8_t *)dst + 32, dst_stride, (const uint8_t *)src,
                     src_stride, size, block_len, nshards, c->stream);
@@ -1646,8 +1663,13 @@ int gfrs_repair_batch(gfrs_ctx *ctx, void *base, size_t shard_len,
     int nglobad = 0;
     for (int i = 0; i < nbad; i++)
       if (bad_idx[i] < t.n + t.m) nglobad++;
+    /* The kernel carries 4 rows: nbad rebuild rows plus one check row per
+     * surviving parity that is not an input, m + l rows in all.  A tactic
+     * with m + l > 4 (RS(6+6)) would drop check rows and pass stripes the
+     * reference Verify fails, so it takes the legacy path. */
     if ((t.l == 0 || cc->fused_lrc_ok) && block_len == 65536 && t.m >= 1 &&
-        t.n + t.m + t.l <= 16 && nglobad <= t.m && nbad <= 4 &&
+        t.m + t.l <= 4 && t.n + t.m + t.l <= 16 && nglobad <= t.m &&
+        nbad <= 4 &&
         (shard_len >= fmin || shard_len <= 4096) && dst_stride % 4 == 0 &&
         nstripes > 0) {
       const int k = t.n, m = t.m;
@@ -1786,6 +1808,10 @@ int gfrs_repair_batch(gfrs_ctx *ctx, void *base, size_t shard_len,
       /* id arrays for every (stripe, bad) image, caller's column order;
        * headers themselves are built by the finalize kernel */
       const size_t nimg = size_t(nstripes) * nbad, idbytes = nimg * 8;
+      if (cc->ids_pending) { /* a queued gfrs_shard_write_batch upload */
+        HIP_TRY(hipEventSynchronize(cc->ids_ev));
+        cc->ids_pending = false;
+      }
       if ((rc2 = cc->stage_pin.ensure(idbytes * 2)) != GFRS_OK) return rc2;
       memcpy(cc->stage_pin.p, bids, idbytes);
       memcpy((uint8_t *)cc->stage_pin.p + idbytes, vuids, idbytes);

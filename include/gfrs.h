@@ -34,6 +34,15 @@
  *    crc32b_encode_batch composition the parity shards inside `base` are
  *    written too (encode_batch's declared output), the fused paths leave
  *    them untouched.
+ *
+ * Verdict contract (pinned by tests/test_gpu_verdict_sweep.py and
+ * tests/test_gpu_verdict_crc.py, next to tests/test_gpu_layout.py): the
+ * fail bitmap of gfrs_reconstruct_verify_batch, gfrs_repair_batch and
+ * gfrs_reconstruct_batch + gfrs_verify_batch equals the reference's
+ * Reconstruct followed by Verify on the same bytes, local stripes
+ * included, for every erasure pattern and whichever surviving column is
+ * corrupted; bad_block / err of the crc32block, sized-coder and shard-image
+ * entry points equal the reference's answer for the same image.
  */
 #ifndef GFRS_H
 #define GFRS_H
@@ -275,7 +284,9 @@ int gfrs_update_idx(gfrs_ctx *ctx, const void *old_shard,
  * UNSPECIFIED after the call (the reference worker also only consumes
  * the repaired bytes through the written bids).  For LRC the surviving
  * local parities serve as extra verify equations, so corruption is
- * detected even when the global stripe has no spare parity.
+ * detected even when the global stripe has no spare parity.  The fused
+ * kernel carries m + l <= 4 rows (rebuilt + checked); wider tactics
+ * (e.g. RS(6+6)) reconstruct in place, verify every parity and then frame.
  *   disk_dst: nstripes*nbad images, image (s,b) at
  *             disk_dst + (s*nbad + b)*dst_stride
  *   bids/vuids: one per (stripe, bad shard), same order
