@@ -10,7 +10,7 @@
  *   reedsolomon.go:220-244 buildMatrix (the default; CubeFS never selects
  *     Cauchy/Jerasure/PAR1, reedsolomon.go:471-472)
  */
-#include "gfrs_internal.h"
+#include "gfrs_plan.h"
 
 #include <cstring>
 

@@ -11,6 +11,10 @@
  *                                            here a bitmask-keyed map
  *   codemode local stripe layout             (codemode.go:301-318)
  *
+ * Which coefficients multiply which shards is decided in gfrs_plan.cpp
+ * (host-only, testable without a device); this file caches and uploads
+ * those plans, stages memory, picks the kernel for a shape and launches.
+ *
  * GPU-only by design: no CPU compute fallback exists.  When no HIP device
  * is visible every compute call fails with GFRS_ERR_NO_GPU.
  */
@@ -21,6 +25,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <set>
@@ -45,6 +50,10 @@ static inline PlanKey plan_key_tag(uint64_t tag) {
 
 static inline void plan_key_set(PlanKey &k, int i) {
   k[size_t(i) >> 6] |= 1ull << (unsigned(i) & 63u);
+}
+
+static inline bool plan_key_test(const PlanKey &k, int i) {
+  return (k[size_t(i) >> 6] >> (unsigned(i) & 63u)) & 1u;
 }
 
 static thread_local std::string g_err;
@@ -121,17 +130,20 @@ struct PinBuf {
   }
 };
 
-/* An uploaded coding plan: index lists + per-coefficient nibble tables. */
+/* An uploaded coding plan: index lists + per-coefficient tables. */
 struct DevPlan {
   DevBuf in_idx, out_idx, tabs;
-  int k = 0, nout = 0;
-  int upload(const std::vector<int32_t> &in, const std::vector<int32_t> &out,
-             const std::vector<uint8_t> &rows /* nout*k coefficients */,
-             hipStream_t s, int rowk = -1 /* row width; in may carry extra
-             (cmp) indices after the first rowk inputs */) {
+  int k = 0, nout = 0; /* row width (in_idx may carry extra cmp indices
+                          after the first k inputs), output rows */
+  uint32_t cmp_mask = 0;
+  const int32_t *in() const { return (const int32_t *)in_idx.p; }
+  const int32_t *out() const { return (const int32_t *)out_idx.p; }
+  const uint8_t *tab() const { return (const uint8_t *)tabs.p; }
+  int upload(const Plan &pl, hipStream_t s) {
     const GfTables &t = gft();
-    k = rowk >= 0 ? rowk : int(in.size());
-    nout = int(out.size());
+    k = pl.rowk;
+    nout = int(pl.out.size());
+    cmp_mask = pl.cmp_mask;
     /* 3-way linear-split tables, 32 B per coefficient (A8|B8|C4|pad):
      * GF(2^8) multiply-by-constant is GF(2)-linear, so mul_c(b) =
      * A[b&7] ^ B[(b>>3)&7] ^ C[b>>6] with A[i]=mul(c,i), B[i]=mul(c,8i),
@@ -142,7 +154,7 @@ struct DevPlan {
     std::vector<uint8_t> tb(size_t(nout) * k * 32, 0);
     for (int r = 0; r < nout; r++)
       for (int c = 0; c < k; c++) {
-        uint8_t coef = rows[size_t(r) * k + c];
+        uint8_t coef = pl.rows[size_t(r) * k + c];
         uint8_t *lt = &tb[(size_t(r) * k + c) * 32];
         for (int i = 0; i < 8; i++) {
           lt[i] = t.mul[coef][i];
@@ -151,12 +163,12 @@ struct DevPlan {
         for (int i = 0; i < 4; i++) lt[16 + i] = t.mul[coef][64 * i];
       }
     int rc;
-    if ((rc = in_idx.ensure(in.size() * 4)) != GFRS_OK) return rc;
-    if ((rc = out_idx.ensure(out.size() * 4)) != GFRS_OK) return rc;
+    if ((rc = in_idx.ensure(pl.in.size() * 4)) != GFRS_OK) return rc;
+    if ((rc = out_idx.ensure(pl.out.size() * 4)) != GFRS_OK) return rc;
     if ((rc = tabs.ensure(tb.size())) != GFRS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(in_idx.p, in.data(), in.size() * 4,
+    HIP_TRY(hipMemcpyAsync(in_idx.p, pl.in.data(), pl.in.size() * 4,
                            hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(out_idx.p, out.data(), out.size() * 4,
+    HIP_TRY(hipMemcpyAsync(out_idx.p, pl.out.data(), pl.out.size() * 4,
                            hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(tabs.p, tb.data(), tb.size(),
                            hipMemcpyHostToDevice, s));
@@ -164,6 +176,8 @@ struct DevPlan {
     return GFRS_OK;
   }
 };
+
+typedef std::map<PlanKey, DevPlan *> PlanCache;
 
 /* One independent execution lane: own stream + own scratch, so
  * concurrent single-stripe callers on one context (the reference shares
@@ -188,17 +202,12 @@ struct LaneView {
 };
 
 struct gfrs_ctx_impl {
-  gfrs_tactic t{};
-  int total = 0;   /* n+m+l */
-  int local_n = 0; /* (n+m)/az when l>0 */
-  int local_m = 0; /* l/az */
+  Code code; /* tactic + encode matrices (gfrs_plan.h) */
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   std::mutex mu;
 
-  std::vector<uint8_t> enc_matrix;   /* (n+m)×n */
-  std::vector<uint8_t> local_matrix; /* (local_n+local_m)×local_n */
   DevPlan enc_plan;                  /* global encode */
   std::vector<DevPlan *> local_enc;  /* per-AZ local encode (global idx) */
   DevPlan local_plan;                /* local engine, identity idx (one
@@ -212,8 +221,9 @@ struct gfrs_ctx_impl {
    * n+m=256 shards, so a packed-u64 key would silently collide distinct
    * missing sets above 58 shards (and 1ull<<i is UB at i>=64); the wide
    * key makes every reachable engine collision-free. */
-  std::map<PlanKey, DevPlan *> dec_cache; /* missing-bitmask → data decode */
-  std::map<PlanKey, DevPlan *> par_cache; /* missing-bitmask → parity rows */
+  PlanCache dec_cache; /* missing-bitmask → data decode (engine tags 1,
+                          2+az, 50) and the bad-set namespaces 60-63 */
+  PlanCache par_cache; /* missing-bitmask → parity rows */
 
   DevBuf ptr_buf;   /* pointer tables for pointer-mode launches */
   DevBuf fail_buf;  /* verify flags / crc bad blocks */
@@ -292,30 +302,43 @@ static inline LaneView view_of(Lane *L) {
                   &L->stage_pin};
 }
 
-/* local stripe global indices for one AZ (codemode.go:301-318) */
-static std::vector<int32_t> local_stripe(const gfrs_tactic &t, int az_idx) {
-  int ln = t.n / t.az_count, lm = t.m / t.az_count, ll = t.l / t.az_count;
-  std::vector<int32_t> idx;
-  idx.reserve(ln + lm + ll);
-  for (int i = 0; i < ln; i++) idx.push_back(az_idx * ln + i);
-  for (int i = 0; i < lm; i++) idx.push_back(t.n + az_idx * lm + i);
-  for (int i = 0; i < ll; i++) idx.push_back(t.n + t.m + az_idx * ll + i);
-  return idx;
-}
-
-static bool tactic_valid(const gfrs_tactic *t) {
-  /* codemode.go:291-299 IsValid; replicate modes (m==0, l==0) are legal —
-   * ec.NewEncoder accepts them and Encode is a no-op (reedsolomon.go:442) */
-  if (!t) return false;
-  if (t->m == 0 && t->l == 0)
-    return t->n > 0 && t->az_count > 0 && t->n % t->az_count == 0;
-  if (t->n <= 0 || t->m <= 0 || t->l < 0 || t->az_count <= 0) return false;
-  if (t->n % t->az_count || t->m % t->az_count || t->l % t->az_count)
-    return false;
-  if (t->n + t->m > 256) return false;
-  if (t->l > 0 && (t->n + t->m) / t->az_count + t->l / t->az_count > 256)
-    return false;
-  return true;
+/* The plans a context keeps for its lifetime: global encode, per-AZ local
+ * encode, the local engine with identity indices, and (where the fused
+ * kernels serve the tactic) the composed LRC encode. */
+static bool upload_fixed_plans(gfrs_ctx_impl *c) {
+  const Code &cd = c->code;
+  const gfrs_tactic &t = cd.t;
+  bool ok = true;
+  /* an engine's encode plan is its parity plan with every parity missing */
+  auto encode_plan = [&](int k, int m, const std::vector<uint8_t> &matrix,
+                         const std::vector<int32_t> &idx, DevPlan *dp) {
+    std::vector<uint8_t> present(k + m, 0);
+    std::fill_n(present.begin(), k, 1);
+    Plan pl;
+    plan_parity(Engine{k, m, matrix.data(), idx.data()}, present.data(), &pl);
+    return dp->upload(pl, c->stream) == GFRS_OK;
+  };
+  std::vector<int32_t> ident(256);
+  for (int i = 0; i < 256; i++) ident[i] = i;
+  if (ok && t.m > 0)
+    ok = encode_plan(t.n, t.m, cd.enc_matrix, ident, &c->enc_plan);
+  if (ok && t.l > 0) {
+    for (int az = 0; az < t.az_count && ok; az++) {
+      c->local_enc.push_back(new DevPlan());
+      ok = encode_plan(cd.local_n, cd.local_m, cd.local_matrix,
+                       local_stripe(t, az), c->local_enc.back());
+    }
+    if (ok) /* one local-stripe set, identity indices */
+      ok = encode_plan(cd.local_n, cd.local_m, cd.local_matrix, ident,
+                       &c->local_plan);
+    if (ok && t.m + t.l <= 4 && cd.total <= 16) {
+      Plan pl;
+      plan_fused_lrc(cd, &pl);
+      ok = c->fused_lrc.upload(pl, c->stream) == GFRS_OK;
+      c->fused_lrc_ok = ok;
+    }
+  }
+  return ok;
 }
 
 }  // namespace gfrs
@@ -379,8 +402,6 @@ gfrs_ctx *gfrs_create(const gfrs_tactic *t, int device) {
   if (ensure_device_init(device) != GFRS_OK) return nullptr;
 
   auto *c = new gfrs_ctx_impl();
-  c->t = *t;
-  c->total = t->n + t->m + t->l;
   c->device = device;
 
   int prev = -1;
@@ -400,84 +421,7 @@ gfrs_ctx *gfrs_create(const gfrs_tactic *t, int device) {
     }
   }
 
-  /* global encode matrix (reedsolomon.go:220-244); replicate modes have
-   * no parity engine (reedsolomon.go:442 parityShards==0 early return) */
-  if (ok && t->m > 0) {
-    c->enc_matrix.resize(size_t(t->n + t->m) * t->n);
-    ok = gf_build_matrix(t->n, t->n + t->m, c->enc_matrix.data());
-    if (ok) {
-      std::vector<int32_t> in(t->n), out(t->m);
-      for (int i = 0; i < t->n; i++) in[i] = i;
-      for (int i = 0; i < t->m; i++) out[i] = t->n + i;
-      std::vector<uint8_t> rows(c->enc_matrix.begin() + size_t(t->n) * t->n,
-                                c->enc_matrix.end());
-      ok = c->enc_plan.upload(in, out, rows, c->stream) == GFRS_OK;
-    }
-  }
-  /* local engines (encoder.go:92-104) */
-  if (ok && t->l > 0) {
-    c->local_n = (t->n + t->m) / t->az_count;
-    c->local_m = t->l / t->az_count;
-    c->local_matrix.resize(size_t(c->local_n + c->local_m) * c->local_n);
-    ok = gf_build_matrix(c->local_n, c->local_n + c->local_m,
-                         c->local_matrix.data());
-    if (ok) {
-      std::vector<uint8_t> lrows(
-          c->local_matrix.begin() + size_t(c->local_n) * c->local_n,
-          c->local_matrix.end());
-      for (int az = 0; az < t->az_count && ok; az++) {
-        auto idx = local_stripe(*t, az);
-        std::vector<int32_t> in(idx.begin(), idx.begin() + c->local_n);
-        std::vector<int32_t> out(idx.begin() + c->local_n, idx.end());
-        auto *p = new DevPlan();
-        ok = p->upload(in, out, lrows, c->stream) == GFRS_OK;
-        c->local_enc.push_back(p);
-      }
-      if (ok) {
-        std::vector<int32_t> in(c->local_n), out(c->local_m);
-        for (int i = 0; i < c->local_n; i++) in[i] = i;
-        for (int i = 0; i < c->local_m; i++) out[i] = c->local_n + i;
-        ok = c->local_plan.upload(in, out, lrows, c->stream) == GFRS_OK;
-      }
-      if (ok && t->m + t->l <= 4 && t->n + t->m + t->l <= 16) {
-        /* compose every output (global parity AND local parity) as a row
-         * over the n data shards: a local input that is a data shard
-         * contributes its coefficient directly; one that is a global
-         * parity contributes localcoef x its parity row (GF linearity) */
-        const GfTables &gt2 = gft();
-        std::vector<int32_t> in(t->n), out;
-        std::vector<uint8_t> rows;
-        for (int i = 0; i < t->n; i++) in[i] = i;
-        for (int p2 = 0; p2 < t->m; p2++) {
-          out.push_back(t->n + p2);
-          const uint8_t *er = &c->enc_matrix[size_t(t->n + p2) * t->n];
-          rows.insert(rows.end(), er, er + t->n);
-        }
-        for (int az = 0; az < t->az_count; az++) {
-          auto idx = local_stripe(*t, az);
-          for (int lp = 0; lp < c->local_m; lp++) {
-            std::vector<uint8_t> row(t->n, 0);
-            const uint8_t *lr =
-                &c->local_matrix[size_t(c->local_n + lp) * c->local_n];
-            for (int j = 0; j < c->local_n; j++) {
-              const int g2i = idx[j];
-              if (g2i < t->n) {
-                row[g2i] ^= lr[j];
-              } else { /* global parity input */
-                const uint8_t *er = &c->enc_matrix[size_t(g2i) * t->n];
-                for (int d = 0; d < t->n; d++)
-                  row[d] ^= gt2.mul[lr[j]][er[d]];
-              }
-            }
-            out.push_back(t->n + t->m + az * c->local_m + lp);
-            rows.insert(rows.end(), row.begin(), row.end());
-          }
-        }
-        ok = c->fused_lrc.upload(in, out, rows, c->stream) == GFRS_OK;
-        c->fused_lrc_ok = ok;
-      }
-    }
-  }
+  ok = ok && code_build(*t, &c->code) && upload_fixed_plans(c);
   if (prev >= 0) hipSetDevice(prev);
   if (!ok) {
     seterr("gfrs_create: init failed (%s)", g_err.c_str());
@@ -510,7 +454,7 @@ int gfrs_synchronize(gfrs_ctx *ctx) {
 
 int gfrs_encode_matrix(gfrs_ctx *ctx, uint8_t *out) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  memcpy(out, c->enc_matrix.data(), c->enc_matrix.size());
+  memcpy(out, c->code.enc_matrix.data(), c->code.enc_matrix.size());
   return GFRS_OK;
 }
 
@@ -546,103 +490,191 @@ static int upload_ptrs(const LaneView &lv, void *const *shards, int nshards) {
   return GFRS_OK;
 }
 
-/* decode plan for a missing pattern (bitmask over all shards of the
- * engine's k+m space).  Mirrors inversion_tree caching. */
-static int get_decode_plan(gfrs_ctx_impl *c, int k, int m,
-                           const std::vector<uint8_t> &matrix,
-                           const std::vector<int> &engine_idx /* global ids */,
-                           const std::vector<uint8_t> &present,
-                           DevPlan **out_plan, int tag, hipStream_t s) {
-  std::lock_guard<std::mutex> cache_lk(c->cache_mu);
-  /* key = missing bitmask + engine tag (global=1, az-local=2+az, ...):
-   * global and local engines can share k, first index AND mask, so the
-   * tag is load-bearing (a collision here once wrote a local parity row
-   * over a global one — caught by the randomized fuzz test) */
-  PlanKey key = plan_key_tag(uint64_t(tag));
-  for (int i = 0; i < k + m; i++)
-    if (!present[i]) plan_key_set(key, i);
-  auto it = c->dec_cache.find(key);
-  if (it != c->dec_cache.end()) {
-    *out_plan = it->second;
-    return GFRS_OK;
-  }
-  /* build: first k valid rows (reedsolomon.go:1453-1466) */
-  std::vector<int> valid;
-  for (int i = 0; i < k + m && int(valid.size()) < k; i++)
-    if (present[i]) valid.push_back(i);
-  if (int(valid.size()) < k) return GFRS_ERR_TOO_FEW_SHARDS;
-  std::vector<uint8_t> sub(size_t(k) * k), inv(size_t(k) * k);
-  for (int r = 0; r < k; r++)
-    memcpy(&sub[size_t(r) * k], &matrix[size_t(valid[r]) * k], k);
-  if (!gf_invert(sub.data(), k, inv.data())) return GFRS_ERR_SINGULAR;
-
-  std::vector<int32_t> in, out;
-  std::vector<uint8_t> rows;
-  for (int r = 0; r < k; r++) in.push_back(engine_idx[valid[r]]);
-  for (int i = 0; i < k; i++)
-    if (!present[i]) {
-      out.push_back(engine_idx[i]);
-      rows.insert(rows.end(), &inv[size_t(i) * k], &inv[size_t(i) * k + k]);
-    }
-  auto *p = new DevPlan();
-  int rc = p->upload(in, out, rows, s);
-  if (rc != GFRS_OK) {
-    delete p;
-    return rc;
-  }
-  c->dec_cache[key] = p;
-  *out_plan = p;
+/* Stage a host stripe: pin, gather the first ncopy shards that are present
+ * (present == nullptr: all), H2D those ncopy shards.  The device and pinned
+ * images hold nshards shards (+ dev_slack device bytes); what is copied
+ * back, and when, is the caller's rule. */
+static int stage_host_stripe(const LaneView &lv, void *const *shards,
+                             int nshards, int ncopy, const uint8_t *present,
+                             size_t shard_len, size_t dev_slack = 0) {
+  const size_t tot = size_t(nshards) * shard_len;
+  int rc;
+  if ((rc = lv.stage_dev->ensure(tot + dev_slack)) != GFRS_OK) return rc;
+  if ((rc = lv.stage_pin->ensure(tot)) != GFRS_OK) return rc;
+  uint8_t *pin = (uint8_t *)lv.stage_pin->p;
+  for (int i = 0; i < ncopy; i++)
+    if (!present || present[i])
+      memcpy(pin + size_t(i) * shard_len, shards[i], shard_len);
+  HIP_TRY(hipMemcpyAsync(lv.stage_dev->p, pin, size_t(ncopy) * shard_len,
+                         hipMemcpyHostToDevice, lv.stream));
   return GFRS_OK;
 }
 
-/* parity-regeneration plan for missing parity rows */
-static int get_parity_plan(gfrs_ctx_impl *c, int k, int m,
-                           const std::vector<uint8_t> &matrix,
-                           const std::vector<int> &engine_idx,
-                           const std::vector<uint8_t> &present,
-                           DevPlan **out_plan, int tag, hipStream_t s) {
-  std::lock_guard<std::mutex> cache_lk(c->cache_mu);
-  PlanKey key = plan_key_tag(uint64_t(tag));
-  for (int i = 0; i < k + m; i++)
-    if (!present[i]) plan_key_set(key, i);
-  auto it = c->par_cache.find(key);
-  if (it != c->par_cache.end()) {
-    *out_plan = it->second;
-    return GFRS_OK;
+/* Stage n bids then n vuids into c->ptr_buf (stream-ordered scratch reuse)
+ * through the pinned staging.  gfrs_shard_write_batch returns with this
+ * upload still queued, so a queued earlier one is waited out before the
+ * staging is refilled. */
+static int stage_ids(gfrs_ctx_impl *c, const uint64_t *bids,
+                     const uint64_t *vuids, size_t n) {
+  const size_t idbytes = n * 8;
+  int rc;
+  if (c->ids_pending) {
+    HIP_TRY(hipEventSynchronize(c->ids_ev));
+    c->ids_pending = false;
   }
-  std::vector<int32_t> in, out;
-  std::vector<uint8_t> rows;
-  for (int i = 0; i < k; i++) in.push_back(engine_idx[i]);
-  for (int i = k; i < k + m; i++)
-    if (!present[i]) {
-      out.push_back(engine_idx[i]);
-      rows.insert(rows.end(), &matrix[size_t(i) * k],
-                  &matrix[size_t(i) * k + k]);
-    }
-  if (out.empty()) {
-    *out_plan = nullptr;
-    return GFRS_OK;
-  }
-  auto *p = new DevPlan();
-  int rc = p->upload(in, out, rows, s);
-  if (rc != GFRS_OK) {
-    delete p;
-    return rc;
-  }
-  c->par_cache[key] = p;
-  *out_plan = p;
+  if ((rc = c->stage_pin.ensure(idbytes * 2)) != GFRS_OK) return rc;
+  memcpy(c->stage_pin.p, bids, idbytes);
+  memcpy((uint8_t *)c->stage_pin.p + idbytes, vuids, idbytes);
+  if ((rc = c->ptr_buf.ensure(idbytes * 2)) != GFRS_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(c->ptr_buf.p, c->stage_pin.p, idbytes * 2,
+                         hipMemcpyHostToDevice, c->stream));
   return GFRS_OK;
 }
 
-/* Run one engine's reconstruct over pointer-mode shards.
- * engine_idx maps engine-local 0..k+m-1 to global shard slots. */
-static int reconstruct_engine(gfrs_ctx_impl *c, const LaneView &lv, int k,
-                              int m, const std::vector<uint8_t> &matrix,
-                              const std::vector<int> &engine_idx,
+/* Per-stripe fail words: begin clears them ahead of the launches ... */
+static int fail_begin(DevBuf *fail, int nstripes, hipStream_t s) {
+  int rc = fail->ensure(size_t(nstripes) * 4);
+  if (rc != GFRS_OK) return rc;
+  HIP_TRY(hipMemsetAsync(fail->p, 0, size_t(nstripes) * 4, s));
+  return GFRS_OK;
+}
+
+/* ... finish reads them back, syncs the stream and packs them: one bit per
+ * stripe into fail_bitmap and/or one flag for the whole call into ok. */
+static int fail_finish(DevBuf *fail, int nstripes, hipStream_t s,
+                       uint64_t *fail_bitmap, int *ok = nullptr) {
+  uint32_t one = 0; /* the single-stripe calls stay off the heap */
+  std::vector<uint32_t> many(nstripes > 1 ? nstripes : 0);
+  uint32_t *fails = nstripes > 1 ? many.data() : &one;
+  HIP_TRY(hipMemcpyAsync(fails, fail->p, size_t(nstripes) * 4,
+                         hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (fail_bitmap) memset(fail_bitmap, 0, ((nstripes + 63) / 64) * 8);
+  if (ok) *ok = 1;
+  for (int i = 0; i < nstripes; i++)
+    if (fails[i]) {
+      if (fail_bitmap) fail_bitmap[i / 64] |= 1ull << (i % 64);
+      if (ok) *ok = 0;
+    }
+  return GFRS_OK;
+}
+
+/* Where a launch finds its shards: a pointer table (nptr > 0: nptr
+ * pointers per stripe) or a strided batch (stripe s shard i at
+ * base + s*stride + i*shard_len). */
+struct Shards {
+  const uint64_t *ptrs;
+  int nptr;
+  uint64_t base, stride;
+};
+static inline Shards table_of(const LaneView &lv, int nptr) {
+  return Shards{(const uint64_t *)lv.ptr_buf->p, nptr, 0, 0};
+}
+static inline Shards strided(const void *base, size_t stride) {
+  return Shards{nullptr, 0, (uint64_t)base, stride};
+}
+
+enum PlanOp {
+  OP_APPLY,  /* out = rows x in */
+  OP_VERIFY, /* compare every row, OR into fail[s] */
+  OP_XOR,    /* out ^= rows x in (pointer tables only) */
+  OP_MIXED,  /* write or compare per p.cmp_mask (strided only) */
+};
+
+/* The one way a plan reaches a kernel. */
+static void run_plan(PlanOp op, const DevPlan &p, const Shards &sh,
+                     size_t shard_len, int nstripes, hipStream_t s,
+                     uint32_t *fail = nullptr) {
+  const bool tab = sh.nptr > 0;
+  switch (op) {
+    case OP_APPLY:
+      if (tab)
+        launch_rs_apply(sh.ptrs, sh.nptr, p.in(), p.k, p.out(), p.nout,
+                        p.tab(), shard_len, nstripes, s);
+      else
+        launch_rs_apply_strided(sh.base, sh.stride, p.in(), p.k, p.out(),
+                                p.nout, p.tab(), shard_len, nstripes, s);
+      break;
+    case OP_VERIFY:
+      if (tab)
+        launch_rs_verify(sh.ptrs, sh.nptr, p.in(), p.k, p.out(), p.nout,
+                         p.tab(), shard_len, nstripes, fail, s);
+      else
+        launch_rs_verify_strided(sh.base, sh.stride, p.in(), p.k, p.out(),
+                                 p.nout, p.tab(), shard_len, nstripes, fail,
+                                 s);
+      break;
+    case OP_XOR:
+      launch_rs_apply_xor(sh.ptrs, sh.nptr, p.in(), p.k, p.out(), p.nout,
+                          p.tab(), shard_len, nstripes, s);
+      break;
+    case OP_MIXED:
+      launch_rs_apply_mixed_strided(sh.base, sh.stride, p.in(), p.k, p.out(),
+                                    p.nout, p.tab(), p.cmp_mask, shard_len,
+                                    nstripes, fail, s);
+      break;
+  }
+}
+
+/* global encode / verify: the global plan, then every AZ's local plan */
+static void run_encode_plans(PlanOp op, const gfrs_ctx_impl *c,
+                             const Shards &sh, size_t shard_len, int nstripes,
+                             hipStream_t s, uint32_t *fail = nullptr) {
+  run_plan(op, c->enc_plan, sh, shard_len, nstripes, s, fail);
+  for (auto *lp : c->local_enc)
+    run_plan(op, *lp, sh, shard_len, nstripes, s, fail);
+}
+
+/* Find the plan cached under `key`, or build, upload and insert it.
+ * cache_mu is held throughout (lanes look plans up concurrently and bypass
+ * c->mu); the build itself runs under the context or lane mutex the caller
+ * already holds.  A hit costs the one lock and the map lookup.  A builder
+ * that leaves `out` empty has nothing to do: *out = nullptr, not cached.
+ * Pass the builder as std::ref(lambda) so that no closure is copied. */
+static int cached_plan(gfrs_ctx_impl *c, PlanCache &cache, const PlanKey &key,
+                       hipStream_t s,
+                       const std::function<int(Plan *)> &build,
+                       DevPlan **out) {
+  std::lock_guard<std::mutex> cache_lk(c->cache_mu);
+  auto it = cache.find(key);
+  if (it != cache.end()) {
+    *out = it->second;
+    return GFRS_OK;
+  }
+  Plan pl;
+  int rc = build(&pl);
+  if (rc != GFRS_OK) return rc;
+  *out = nullptr;
+  if (pl.out.empty()) return GFRS_OK;
+  auto p = std::make_unique<DevPlan>();
+  if ((rc = p->upload(pl, s)) != GFRS_OK) return rc;
+  *out = cache[key] = p.release();
+  return GFRS_OK;
+}
+
+/* Key of a bad list in namespace `tag`; refuses out-of-range indices and,
+ * unless dup_ok, duplicates (a duplicate would alias the key of the set
+ * without it, whose plan has fewer write rows). */
+static int bad_list_key(uint64_t tag, const int32_t *bad, int nbad, int total,
+                        bool dup_ok, PlanKey *key) {
+  *key = plan_key_tag(tag);
+  for (int i = 0; i < nbad; i++) {
+    if (bad[i] < 0 || bad[i] >= total) return GFRS_ERR_INVALID_SHARDS;
+    if (!dup_ok && plan_key_test(*key, bad[i])) return GFRS_ERR_INVALID_SHARDS;
+    plan_key_set(*key, bad[i]);
+  }
+  return GFRS_OK;
+}
+
+/* Run one engine's reconstruct: decode plan for the missing data (mirrors
+ * the inversion_tree cache), then parity plan for the missing parities.
+ * present covers the engine's k+m shards. */
+static int reconstruct_engine(gfrs_ctx_impl *c, const LaneView &lv,
+                              const Engine &e,
                               const std::vector<uint8_t> &present,
                               size_t shard_len, int nstripes, int data_only,
-                              uint64_t strided_base, uint64_t stripe_stride,
-                              int nptr_or_0, int tag) {
+                              const Shards &sh, int tag) {
+  const int k = e.k, m = e.m;
   int npresent = 0, dpresent = 0;
   for (int i = 0; i < k + m; i++)
     if (present[i]) {
@@ -652,62 +684,57 @@ static int reconstruct_engine(gfrs_ctx_impl *c, const LaneView &lv, int k,
   if (npresent == k + m || (data_only && dpresent == k)) return GFRS_OK;
   if (npresent < k) return GFRS_ERR_TOO_FEW_SHARDS;
 
-  DevPlan *dec = nullptr;
-  int rc = GFRS_OK;
-  bool have_missing_data = dpresent < k;
-  if (have_missing_data) {
-    rc = get_decode_plan(c, k, m, matrix, engine_idx, present, &dec, tag,
-                         lv.stream);
+  /* key = missing bitmask + engine tag (global=1, az-local=2+az, ...):
+   * global and local engines can share k, first index AND mask, so the
+   * tag is load-bearing (a collision here once wrote a local parity row
+   * over a global one — caught by the randomized fuzz test) */
+  PlanKey key = plan_key_tag(uint64_t(tag));
+  for (int i = 0; i < k + m; i++)
+    if (!present[i]) plan_key_set(key, i);
+  const uint8_t *pr = present.data();
+  DevPlan *p = nullptr;
+  int rc;
+  if (dpresent < k) { /* missing data */
+    auto build = [&](Plan *pl) { return plan_decode(e, pr, pl); };
+    rc = cached_plan(c, c->dec_cache, key, lv.stream, std::ref(build), &p);
     if (rc != GFRS_OK) return rc;
-    if (nptr_or_0 > 0)
-      launch_rs_apply(reinterpret_cast<const uint64_t *>(lv.ptr_buf->p),
-                      nptr_or_0, (const int32_t *)dec->in_idx.p, dec->k,
-                      (const int32_t *)dec->out_idx.p, dec->nout,
-                      (const uint8_t *)dec->tabs.p, shard_len, nstripes,
-                      lv.stream);
-    else
-      launch_rs_apply_strided(strided_base, stripe_stride,
-                              (const int32_t *)dec->in_idx.p, dec->k,
-                              (const int32_t *)dec->out_idx.p, dec->nout,
-                              (const uint8_t *)dec->tabs.p, shard_len,
-                              nstripes, lv.stream);
+    run_plan(OP_APPLY, *p, sh, shard_len, nstripes, lv.stream);
   }
   if (!data_only) {
-    DevPlan *par = nullptr;
-    rc = get_parity_plan(c, k, m, matrix, engine_idx, present, &par, tag,
-                         lv.stream);
+    auto build = [&](Plan *pl) { return plan_parity(e, pr, pl); };
+    rc = cached_plan(c, c->par_cache, key, lv.stream, std::ref(build), &p);
     if (rc != GFRS_OK) return rc;
-    if (par) {
-      if (nptr_or_0 > 0)
-        launch_rs_apply(reinterpret_cast<const uint64_t *>(lv.ptr_buf->p),
-                        nptr_or_0, (const int32_t *)par->in_idx.p, par->k,
-                        (const int32_t *)par->out_idx.p, par->nout,
-                        (const uint8_t *)par->tabs.p, shard_len, nstripes,
-                        lv.stream);
-      else
-        launch_rs_apply_strided(strided_base, stripe_stride,
-                                (const int32_t *)par->in_idx.p, par->k,
-                                (const int32_t *)par->out_idx.p, par->nout,
-                                (const uint8_t *)par->tabs.p, shard_len,
-                                nstripes, lv.stream);
-    }
+    if (p) run_plan(OP_APPLY, *p, sh, shard_len, nstripes, lv.stream);
   }
   return GFRS_OK;
+}
+
+/* one local stripe set given on its own (lrcencoder.go:94-99,147-153) */
+static int reconstruct_local_form(gfrs_ctx_impl *c, const LaneView &lv,
+                                  const std::vector<uint8_t> &present,
+                                  size_t shard_len, int data_only,
+                                  const Shards &sh) {
+  const Code &cd = c->code;
+  std::vector<int32_t> li(present.size());
+  for (size_t i = 0; i < li.size(); i++) li[i] = int32_t(i);
+  const Engine e{cd.local_n, cd.local_m, cd.local_matrix.data(), li.data()};
+  return reconstruct_engine(c, lv, e, present, shard_len, 1, data_only, sh,
+                            /*tag=*/50);
 }
 
 /* Core reconstruct across global + local engines.  present covers all
  * n+m+l global slots. */
 static int reconstruct_all(gfrs_ctx_impl *c, const LaneView &lv,
                            std::vector<uint8_t> &present, size_t shard_len,
-                           int nstripes, int data_only, uint64_t base,
-                           uint64_t stride, int nptr_or_0) {
-  const gfrs_tactic &t = c->t;
-  std::vector<int> gidx(t.n + t.m);
+                           int nstripes, int data_only, const Shards &sh) {
+  const Code &cd = c->code;
+  const gfrs_tactic &t = cd.t;
+  std::vector<int32_t> gidx(t.n + t.m);
   for (int i = 0; i < t.n + t.m; i++) gidx[i] = i;
   std::vector<uint8_t> gpresent(present.begin(), present.begin() + t.n + t.m);
-  int rc = reconstruct_engine(c, lv, t.n, t.m, c->enc_matrix, gidx, gpresent,
-                              shard_len, nstripes, data_only, base, stride,
-                              nptr_or_0, /*tag=*/1);
+  const Engine g{t.n, t.m, cd.enc_matrix.data(), gidx.data()};
+  int rc = reconstruct_engine(c, lv, g, gpresent, shard_len, nstripes,
+                              data_only, sh, /*tag=*/1);
   if (rc != GFRS_OK) return rc;
   if (t.l == 0 || data_only) return GFRS_OK;
   /* regenerate bad local parities per AZ (lrcencoder.go:160-184); after
@@ -716,15 +743,15 @@ static int reconstruct_all(gfrs_ctx_impl *c, const LaneView &lv,
     auto idx = local_stripe(t, az);
     bool need = false;
     std::vector<uint8_t> lp(idx.size());
-    std::vector<int> li(idx.begin(), idx.end());
     for (size_t i = 0; i < idx.size(); i++) {
       lp[i] = idx[i] < t.n + t.m ? 1 : present[idx[i]];
       if (!lp[i]) need = true;
     }
     if (!need) continue;
-    rc = reconstruct_engine(c, lv, c->local_n, c->local_m, c->local_matrix,
-                            li, lp, shard_len, nstripes, /*data_only=*/0,
-                            base, stride, nptr_or_0, /*tag=*/2 + az);
+    const Engine e{cd.local_n, cd.local_m, cd.local_matrix.data(),
+                   idx.data()};
+    rc = reconstruct_engine(c, lv, e, lp, shard_len, nstripes,
+                            /*data_only=*/0, sh, /*tag=*/2 + az);
     if (rc != GFRS_OK) return rc;
   }
   return GFRS_OK;
@@ -739,9 +766,11 @@ extern "C" {
 int gfrs_encode(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
                 int nshards, int memloc) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  if (c->t.m == 0) return nshards == c->total ? GFRS_OK : GFRS_ERR_INVALID_SHARDS;
-  if (nshards != c->total) {
-    seterr("encode: want %d shards, got %d", c->total, nshards);
+  const gfrs_tactic &t = c->code.t;
+  const int total = c->code.total;
+  if (t.m == 0) return nshards == total ? GFRS_OK : GFRS_ERR_INVALID_SHARDS;
+  if (nshards != total) {
+    seterr("encode: want %d shards, got %d", total, nshards);
     return GFRS_ERR_INVALID_SHARDS;
   }
   /* foreground call: fan out over the stream-lane pool so concurrent
@@ -754,23 +783,20 @@ int gfrs_encode(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
   int rc;
   if (memloc == GFRS_MEM_HOST) {
     /* stage contiguous stripe, run strided, copy parity back */
-    size_t tot = size_t(c->total) * shard_len;
-    if ((rc = lv.stage_dev->ensure(tot)) != GFRS_OK) return rc;
-    if ((rc = lv.stage_pin->ensure(tot)) != GFRS_OK) return rc;
+    const size_t tot = size_t(total) * shard_len;
+    if ((rc = stage_host_stripe(lv, shards, total, t.n, nullptr,
+                                shard_len)) != GFRS_OK)
+      return rc;
     uint8_t *pin = (uint8_t *)lv.stage_pin->p;
-    for (int i = 0; i < c->t.n; i++)
-      memcpy(pin + size_t(i) * shard_len, shards[i], shard_len);
     uint8_t *dev = (uint8_t *)lv.stage_dev->p;
-    HIP_TRY(hipMemcpyAsync(dev, pin, size_t(c->t.n) * shard_len,
-                           hipMemcpyHostToDevice, lv.stream));
     rc = encode_batch_impl(c, dev, shard_len, tot, 1, lv.stream);
     if (rc != GFRS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(pin + size_t(c->t.n) * shard_len,
-                           dev + size_t(c->t.n) * shard_len,
-                           size_t(c->t.m + c->t.l) * shard_len,
+    HIP_TRY(hipMemcpyAsync(pin + size_t(t.n) * shard_len,
+                           dev + size_t(t.n) * shard_len,
+                           size_t(t.m + t.l) * shard_len,
                            hipMemcpyDeviceToHost, lv.stream));
     HIP_TRY(hipStreamSynchronize(lv.stream));
-    for (int i = c->t.n; i < c->total; i++)
+    for (int i = t.n; i < total; i++)
       memcpy(shards[i], pin + size_t(i) * shard_len, shard_len);
     return GFRS_OK;
   }
@@ -789,16 +815,7 @@ int gfrs_encode(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
     return GFRS_OK;
   }
   if ((rc = upload_ptrs(lv, shards, nshards)) != GFRS_OK) return rc;
-  launch_rs_apply((const uint64_t *)lv.ptr_buf->p, c->total,
-                  (const int32_t *)c->enc_plan.in_idx.p, c->enc_plan.k,
-                  (const int32_t *)c->enc_plan.out_idx.p, c->enc_plan.nout,
-                  (const uint8_t *)c->enc_plan.tabs.p, shard_len, 1,
-                  lv.stream);
-  for (auto *lp : c->local_enc)
-    launch_rs_apply((const uint64_t *)lv.ptr_buf->p, c->total,
-                    (const int32_t *)lp->in_idx.p, lp->k,
-                    (const int32_t *)lp->out_idx.p, lp->nout,
-                    (const uint8_t *)lp->tabs.p, shard_len, 1, lv.stream);
+  run_encode_plans(OP_APPLY, c, table_of(lv, total), shard_len, 1, lv.stream);
   HIP_TRY(hipStreamSynchronize(lv.stream));
   return GFRS_OK;
 }
@@ -809,17 +826,8 @@ static int encode_batch_impl(gfrs_ctx_impl *c, void *base, size_t shard_len,
                              size_t stripe_stride, int nstripes,
                              hipStream_t st) {
   StreamGuard g(c);
-  launch_rs_apply_strided((uint64_t)base, stripe_stride,
-                          (const int32_t *)c->enc_plan.in_idx.p,
-                          c->enc_plan.k, (const int32_t *)c->enc_plan.out_idx.p,
-                          c->enc_plan.nout, (const uint8_t *)c->enc_plan.tabs.p,
-                          shard_len, nstripes, st);
-  for (auto *lp : c->local_enc)
-    launch_rs_apply_strided((uint64_t)base, stripe_stride,
-                            (const int32_t *)lp->in_idx.p, lp->k,
-                            (const int32_t *)lp->out_idx.p, lp->nout,
-                            (const uint8_t *)lp->tabs.p, shard_len, nstripes,
-                            st);
+  run_encode_plans(OP_APPLY, c, strided(base, stripe_stride), shard_len,
+                   nstripes, st);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail("encode_batch launch", e);
   return GFRS_OK;
@@ -836,94 +844,36 @@ int gfrs_encode_batch(gfrs_ctx *ctx, void *base, size_t shard_len,
 int gfrs_verify(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
                 int nshards, int memloc, int *ok) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  if (c->t.m == 0) { /* zero parity rows: vacuously true (reedsolomon.go:784) */
+  const int total = c->code.total;
+  if (c->code.t.m == 0) { /* zero parity rows: vacuously true (reedsolomon.go:784) */
     *ok = 1;
-    return nshards == c->total ? GFRS_OK : GFRS_ERR_INVALID_SHARDS;
+    return nshards == total ? GFRS_OK : GFRS_ERR_INVALID_SHARDS;
   }
-  bool local_form = c->t.l > 0 && nshards == c->total / c->t.az_count;
-  if (nshards != c->total && !local_form) return GFRS_ERR_INVALID_SHARDS;
+  /* full set or one local stripe set (lrcencoder.go:94-99) */
+  bool local_form = c->code.t.l > 0 && nshards == total / c->code.t.az_count;
+  if (nshards != total && !local_form) return GFRS_ERR_INVALID_SHARDS;
   Lane *L = c->pick_lane();
   std::unique_lock<std::mutex> lk(L ? L->mu : c->mu);
   StreamGuard g(c);
   const LaneView lv = L ? view_of(L) : view_of(c);
-  if (local_form) {
-    /* one local stripe set (lrcencoder.go:94-99) */
-    int rc;
-    if (memloc == GFRS_MEM_HOST) {
-      size_t tot = size_t(nshards) * shard_len;
-      if ((rc = lv.stage_dev->ensure(tot)) != GFRS_OK) return rc;
-      if ((rc = lv.stage_pin->ensure(tot)) != GFRS_OK) return rc;
-      uint8_t *pin = (uint8_t *)lv.stage_pin->p;
-      for (int i = 0; i < nshards; i++)
-        memcpy(pin + size_t(i) * shard_len, shards[i], shard_len);
-      HIP_TRY(hipMemcpyAsync(lv.stage_dev->p, pin, tot,
-                             hipMemcpyHostToDevice, lv.stream));
-      if ((rc = lv.fail_buf->ensure(4)) != GFRS_OK) return rc;
-      HIP_TRY(hipMemsetAsync(lv.fail_buf->p, 0, 4, lv.stream));
-      launch_rs_verify_strided((uint64_t)lv.stage_dev->p, tot,
-                               (const int32_t *)c->local_plan.in_idx.p,
-                               c->local_plan.k,
-                               (const int32_t *)c->local_plan.out_idx.p,
-                               c->local_plan.nout,
-                               (const uint8_t *)c->local_plan.tabs.p,
-                               shard_len, 1, (uint32_t *)lv.fail_buf->p,
-                               lv.stream);
-    } else {
-      if ((rc = upload_ptrs(lv, shards, nshards)) != GFRS_OK) return rc;
-      if ((rc = lv.fail_buf->ensure(4)) != GFRS_OK) return rc;
-      HIP_TRY(hipMemsetAsync(lv.fail_buf->p, 0, 4, lv.stream));
-      launch_rs_verify((const uint64_t *)lv.ptr_buf->p, nshards,
-                       (const int32_t *)c->local_plan.in_idx.p,
-                       c->local_plan.k,
-                       (const int32_t *)c->local_plan.out_idx.p,
-                       c->local_plan.nout,
-                       (const uint8_t *)c->local_plan.tabs.p, shard_len, 1,
-                       (uint32_t *)lv.fail_buf->p, lv.stream);
-    }
-    uint32_t fail = 0;
-    HIP_TRY(hipMemcpyAsync(&fail, lv.fail_buf->p, 4, hipMemcpyDeviceToHost,
-                           lv.stream));
-    HIP_TRY(hipStreamSynchronize(lv.stream));
-    *ok = fail == 0;
-    return GFRS_OK;
-  }
   int rc;
-  const uint64_t *pt;
+  Shards sh;
   if (memloc == GFRS_MEM_HOST) {
-    size_t tot = size_t(c->total) * shard_len;
-    if ((rc = lv.stage_dev->ensure(tot + 64)) != GFRS_OK) return rc;
-    if ((rc = lv.stage_pin->ensure(tot)) != GFRS_OK) return rc;
-    uint8_t *pin = (uint8_t *)lv.stage_pin->p;
-    for (int i = 0; i < c->total; i++)
-      memcpy(pin + size_t(i) * shard_len, shards[i], shard_len);
-    HIP_TRY(hipMemcpyAsync(lv.stage_dev->p, pin, tot, hipMemcpyHostToDevice,
-                           lv.stream));
-    uint64_t fb = 0;
-    rc = verify_batch_impl(c, lv.stage_dev->p, shard_len, tot, 1, &fb,
-                           lv.stream, lv.fail_buf);
-    if (rc != GFRS_OK) return rc;
-    *ok = fb == 0;
-    return GFRS_OK;
+    if ((rc = stage_host_stripe(lv, shards, nshards, nshards, nullptr,
+                                shard_len, local_form ? 0 : 64)) != GFRS_OK)
+      return rc;
+    sh = strided(lv.stage_dev->p, size_t(nshards) * shard_len);
+  } else {
+    if ((rc = upload_ptrs(lv, shards, nshards)) != GFRS_OK) return rc;
+    sh = table_of(lv, nshards);
   }
-  if ((rc = upload_ptrs(lv, shards, nshards)) != GFRS_OK) return rc;
-  if ((rc = lv.fail_buf->ensure(4)) != GFRS_OK) return rc;
-  HIP_TRY(hipMemsetAsync(lv.fail_buf->p, 0, 4, lv.stream));
-  pt = (const uint64_t *)lv.ptr_buf->p;
-  launch_rs_verify(pt, c->total, (const int32_t *)c->enc_plan.in_idx.p,
-                   c->enc_plan.k, (const int32_t *)c->enc_plan.out_idx.p,
-                   c->enc_plan.nout, (const uint8_t *)c->enc_plan.tabs.p,
-                   shard_len, 1, (uint32_t *)lv.fail_buf->p, lv.stream);
-  for (auto *lp : c->local_enc)
-    launch_rs_verify(pt, c->total, (const int32_t *)lp->in_idx.p, lp->k,
-                     (const int32_t *)lp->out_idx.p, lp->nout,
-                     (const uint8_t *)lp->tabs.p, shard_len, 1,
-                     (uint32_t *)lv.fail_buf->p, lv.stream);
-  uint32_t fail = 0;
-  HIP_TRY(hipMemcpyAsync(&fail, lv.fail_buf->p, 4, hipMemcpyDeviceToHost,
-                         lv.stream));
-  HIP_TRY(hipStreamSynchronize(lv.stream));
-  *ok = fail == 0;
-  return GFRS_OK;
+  if ((rc = fail_begin(lv.fail_buf, 1, lv.stream)) != GFRS_OK) return rc;
+  uint32_t *fail = (uint32_t *)lv.fail_buf->p;
+  if (local_form)
+    run_plan(OP_VERIFY, c->local_plan, sh, shard_len, 1, lv.stream, fail);
+  else
+    run_encode_plans(OP_VERIFY, c, sh, shard_len, 1, lv.stream, fail);
+  return fail_finish(lv.fail_buf, 1, lv.stream, nullptr, ok);
 }
 
 static int verify_batch_impl(gfrs_ctx_impl *c, const void *base,
@@ -932,31 +882,10 @@ static int verify_batch_impl(gfrs_ctx_impl *c, const void *base,
                              hipStream_t st, DevBuf *fail) {
   StreamGuard g(c);
   int rc;
-  if ((rc = fail->ensure(size_t(nstripes) * 4)) != GFRS_OK) return rc;
-  HIP_TRY(hipMemsetAsync(fail->p, 0, size_t(nstripes) * 4, st));
-  launch_rs_verify_strided((uint64_t)base, stripe_stride,
-                           (const int32_t *)c->enc_plan.in_idx.p,
-                           c->enc_plan.k,
-                           (const int32_t *)c->enc_plan.out_idx.p,
-                           c->enc_plan.nout,
-                           (const uint8_t *)c->enc_plan.tabs.p, shard_len,
-                           nstripes, (uint32_t *)fail->p, st);
-  for (auto *lp : c->local_enc)
-    launch_rs_verify_strided((uint64_t)base, stripe_stride,
-                             (const int32_t *)lp->in_idx.p, lp->k,
-                             (const int32_t *)lp->out_idx.p, lp->nout,
-                             (const uint8_t *)lp->tabs.p, shard_len, nstripes,
-                             (uint32_t *)fail->p, st);
-  std::vector<uint32_t> fails(nstripes);
-  HIP_TRY(hipMemcpyAsync(fails.data(), fail->p, size_t(nstripes) * 4,
-                         hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (fail_bitmap) {
-    memset(fail_bitmap, 0, ((nstripes + 63) / 64) * 8);
-    for (int s = 0; s < nstripes; s++)
-      if (fails[s]) fail_bitmap[s / 64] |= 1ull << (s % 64);
-  }
-  return GFRS_OK;
+  if ((rc = fail_begin(fail, nstripes, st)) != GFRS_OK) return rc;
+  run_encode_plans(OP_VERIFY, c, strided(base, stripe_stride), shard_len,
+                   nstripes, st, (uint32_t *)fail->p);
+  return fail_finish(fail, nstripes, st, fail_bitmap);
 }
 
 int gfrs_verify_batch(gfrs_ctx *ctx, const void *base, size_t shard_len,
@@ -972,7 +901,7 @@ int gfrs_reconstruct(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
                      int nshards, int memloc, const int32_t *bad_idx,
                      int nbad, int data_only) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  const gfrs_tactic &t = c->t;
+  const gfrs_tactic &t = c->code.t;
   Lane *L = c->pick_lane();
   std::unique_lock<std::mutex> lk(L ? L->mu : c->mu);
   StreamGuard g(c);
@@ -982,8 +911,8 @@ int gfrs_reconstruct(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
   if (t.m == 0) /* no parity: any missing shard is unrecoverable */
     return nbad == 0 ? GFRS_OK : GFRS_ERR_TOO_FEW_SHARDS;
   /* full set or, for LRC, a single local stripe (lrcencoder.go:147-153) */
-  bool local_form = t.l > 0 && nshards == c->total / t.az_count;
-  if (nshards != c->total && !local_form) return GFRS_ERR_INVALID_SHARDS;
+  bool local_form = t.l > 0 && nshards == c->code.total / t.az_count;
+  if (nshards != c->code.total && !local_form) return GFRS_ERR_INVALID_SHARDS;
 
   std::vector<uint8_t> present(nshards, 1);
   for (int i = 0; i < nbad; i++) {
@@ -991,54 +920,36 @@ int gfrs_reconstruct(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
     present[bad_idx[i]] = 0;
   }
 
-  if (memloc == GFRS_MEM_HOST) {
-    /* stage the whole stripe contiguously and run in strided mode */
-    size_t tot = size_t(nshards) * shard_len;
-    if ((rc = lv.stage_dev->ensure(tot)) != GFRS_OK) return rc;
-    if ((rc = lv.stage_pin->ensure(tot)) != GFRS_OK) return rc;
-    uint8_t *pin = (uint8_t *)lv.stage_pin->p;
-    uint8_t *dev = (uint8_t *)lv.stage_dev->p;
-    for (int i = 0; i < nshards; i++)
-      if (present[i]) memcpy(pin + size_t(i) * shard_len, shards[i], shard_len);
-    HIP_TRY(hipMemcpyAsync(dev, pin, tot, hipMemcpyHostToDevice, lv.stream));
-    if (local_form) {
-      std::vector<int> li(nshards);
-      for (int i = 0; i < nshards; i++) li[i] = i;
-      rc = reconstruct_engine(c, lv, c->local_n, c->local_m, c->local_matrix,
-                              li, present, shard_len, 1, data_only,
-                              (uint64_t)dev, tot, 0, /*tag=*/50);
-    } else {
-      rc = reconstruct_all(c, lv, present, shard_len, 1, data_only,
-                           (uint64_t)dev, tot, 0);
-    }
-    if (rc != GFRS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(pin, dev, tot, hipMemcpyDeviceToHost, lv.stream));
-    HIP_TRY(hipStreamSynchronize(lv.stream));
+  /* host memory: stage the whole stripe contiguously, run strided */
+  const bool host = memloc == GFRS_MEM_HOST;
+  const size_t tot = size_t(nshards) * shard_len;
+  if (host)
+    rc = stage_host_stripe(lv, shards, nshards, nshards, present.data(),
+                           shard_len);
+  else
+    rc = upload_ptrs(lv, shards, nshards);
+  if (rc != GFRS_OK) return rc;
+  const Shards sh = host ? strided(lv.stage_dev->p, tot) : table_of(lv, nshards);
+  if (local_form)
+    rc = reconstruct_local_form(c, lv, present, shard_len, data_only, sh);
+  else
+    rc = reconstruct_all(c, lv, present, shard_len, 1, data_only, sh);
+  if (rc != GFRS_OK) return rc;
+  uint8_t *pin = (uint8_t *)lv.stage_pin->p;
+  if (host)
+    HIP_TRY(hipMemcpyAsync(pin, lv.stage_dev->p, tot, hipMemcpyDeviceToHost,
+                           lv.stream));
+  HIP_TRY(hipStreamSynchronize(lv.stream));
+  if (host) {
     /* copy back only shards actually rebuilt: with data_only the engine
      * leaves missing parity untouched (ReconstructData semantics,
      * reedsolomon.go:1441-1444) — overwriting the caller's buffer with
      * stale staging bytes would be wrong */
-    const int ndata = local_form ? c->local_n : t.n;
+    const int ndata = local_form ? c->code.local_n : t.n;
     for (int i = 0; i < nshards; i++)
       if (!present[i] && (!data_only || i < ndata))
         memcpy(shards[i], pin + size_t(i) * shard_len, shard_len);
-    return GFRS_OK;
   }
-
-  if ((rc = upload_ptrs(lv, shards, nshards)) != GFRS_OK) return rc;
-
-  if (local_form) {
-    std::vector<int> li(nshards);
-    for (int i = 0; i < nshards; i++) li[i] = i;
-    rc = reconstruct_engine(c, lv, c->local_n, c->local_m, c->local_matrix,
-                            li, present, shard_len, 1, data_only, 0, 0,
-                            nshards, /*tag=*/50);
-  } else {
-    rc = reconstruct_all(c, lv, present, shard_len, 1, data_only, 0, 0,
-                         nshards);
-  }
-  if (rc != GFRS_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(lv.stream));
   return GFRS_OK;
 }
 
@@ -1048,14 +959,14 @@ int gfrs_reconstruct_batch(gfrs_ctx *ctx, void *base, size_t shard_len,
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
   std::lock_guard<std::mutex> lk(c->mu);
   StreamGuard g(c);
-  std::vector<uint8_t> present(c->total, 1);
+  std::vector<uint8_t> present(c->code.total, 1);
   for (int i = 0; i < nbad; i++) {
-    if (bad_idx[i] < 0 || bad_idx[i] >= c->total)
+    if (bad_idx[i] < 0 || bad_idx[i] >= c->code.total)
       return GFRS_ERR_INVALID_SHARDS;
     present[bad_idx[i]] = 0;
   }
   int rc = reconstruct_all(c, view_of(c), present, shard_len, nstripes,
-                           data_only, (uint64_t)base, stripe_stride, 0);
+                           data_only, strided(base, stripe_stride));
   if (rc != GFRS_OK) return rc;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail("reconstruct_batch launch", e);
@@ -1067,7 +978,7 @@ int gfrs_encode_frame_batch(gfrs_ctx *ctx, void *framed,
                             size_t shard_len, size_t stripe_stride,
                             int nstripes, int64_t block_len) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  const gfrs_tactic &t = c->t;
+  const gfrs_tactic &t = c->code.t;
   if (block_len <= 0 || block_len % 4096) return GFRS_ERR_INVALID_BLOCK;
   if (nstripes <= 0 || shard_len == 0) return GFRS_ERR_INVALID_SHARDS;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -1108,8 +1019,7 @@ int gfrs_encode_frame_batch(gfrs_ctx *ctx, void *framed,
     const DevPlan &pl = t.l == 0 ? c->enc_plan : c->fused_lrc;
     launch_rs_encode_frame_small((uint8_t *)framed, framed_stride,
                                  (uint64_t)base, stripe_stride, shard_len,
-                                 t.n, gm_all, (const uint8_t *)pl.tabs.p,
-                                 nstripes, c->stream);
+                                 t.n, gm_all, pl.tab(), nstripes, c->stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail("encode_frame_small launch", e);
     return GFRS_OK;
@@ -1119,20 +1029,20 @@ int gfrs_encode_frame_batch(gfrs_ctx *ctx, void *framed,
     const DevPlan &pl = t.l == 0 ? c->enc_plan : c->fused_lrc;
     launch_rs_encode_frame((uint8_t *)framed, framed_stride, (uint64_t)base,
                            stripe_stride, shard_len, t.n, gm_all,
-                           (const uint8_t *)pl.tabs.p, nstripes, c->stream);
+                           pl.tab(), nstripes, c->stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail("encode_frame launch", e);
     return GFRS_OK;
   }
   /* fallback composition: needs the contiguous ec.Buffer batch layout */
-  if (stripe_stride != size_t(c->total) * shard_len)
+  if (stripe_stride != size_t(c->code.total) * shard_len)
     return GFRS_ERR_UNSUPPORTED;
   int rc = encode_batch_impl(c, base, shard_len, stripe_stride, nstripes,
                              c->stream);
   if (rc != GFRS_OK) return rc;
   return crc32b_encode_batch_impl(c, framed, framed_stride, base, shard_len,
                                   int64_t(shard_len), block_len,
-                                  nstripes * c->total);
+                                  nstripes * c->code.total);
 }
 
 /* ---------------- sized coder (rpc2 body framing) ---------------- */
@@ -1239,32 +1149,21 @@ int gfrs_shard_write_batch(gfrs_ctx *ctx, void *dst, size_t dst_stride,
   /* ship the raw id arrays; the finalize kernel builds the 32 B headers
    * (shard.go:241-261) on device - host-side construction was the
    * bottleneck at millions of shards per call */
-  const size_t idbytes = size_t(nshards) * 8;
-  /* this call is async, so the previous call's upload may not have read
-   * the staging yet (the legacy repair path issues one call per lost
-   * column back to back: column b then got column b+1's ids) */
-  if (c->ids_pending) {
-    HIP_TRY(hipEventSynchronize(c->ids_ev));
-    c->ids_pending = false;
-  }
+  /* this call is async, so the next call must not refill the staging
+   * before this upload ran (the legacy repair path issues one call per
+   * lost column back to back: column b then got column b+1's ids):
+   * stage_ids waits for the event recorded here */
   if (!c->ids_ev)
     HIP_TRY(hipEventCreateWithFlags(&c->ids_ev, hipEventDisableTiming));
-  if ((rc = c->stage_pin.ensure(idbytes * 2)) != GFRS_OK) return rc;
-  memcpy(c->stage_pin.p, bids, idbytes);
-  memcpy((uint8_t *)c->stage_pin.p + idbytes, vuids, idbytes);
-  DevBuf &hbuf = c->ptr_buf; /* reuse scratch (stream-ordered) */
-  if ((rc = hbuf.ensure(idbytes * 2)) != GFRS_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(hbuf.p, c->stage_pin.p, idbytes * 2,
-                         hipMemcpyHostToDevice, c->stream));
+  if ((rc = stage_ids(c, bids, vuids, size_t(nshards))) != GFRS_OK) return rc;
   HIP_TRY(hipEventRecord(c->ids_ev, c->stream));
   c->ids_pending = true;
+  const uint64_t *ids = (const uint64_t *)c->ptr_buf.p;
   /* framed body at +32 */
   launch_crc_encode((uint8_t *)dst + 32, dst_stride, (const uint8_t *)src,
                     src_stride, size, block_len, nshards, c->stream);
-  launch_shard_finalize((uint8_t *)dst, dst_stride,
-                        (const uint64_t *)hbuf.p,
-                        (const uint64_t *)hbuf.p + nshards, size, block_len,
-                        nshards, c->stream);
+  launch_shard_finalize((uint8_t *)dst, dst_stride, ids, ids + nshards, size,
+                        block_len, nshards, c->stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail("shard_write launch", e);
   return GFRS_OK;
@@ -1313,7 +1212,7 @@ int gfrs_shard_parse_batch(gfrs_ctx *ctx, const void *img, size_t stride,
 int gfrs_encode_idx(gfrs_ctx *ctx, const void *data_shard, int idx,
                     void *const *parity, size_t shard_len, int nparity) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  if (idx < 0 || idx >= c->t.n || nparity != c->t.m)
+  if (idx < 0 || idx >= c->code.t.n || nparity != c->code.t.m)
     return GFRS_ERR_INVALID_SHARDS;
   std::lock_guard<std::mutex> lk(c->mu);
   StreamGuard g(c);
@@ -1322,182 +1221,52 @@ int gfrs_encode_idx(gfrs_ctx *ctx, const void *data_shard, int idx,
   std::vector<void *> ptrs(1 + nparity);
   ptrs[0] = const_cast<void *>(data_shard);
   for (int r = 0; r < nparity; r++) ptrs[1 + r] = parity[r];
-  if ((rc = upload_ptrs(view_of(c), ptrs.data(), int(ptrs.size()))) !=
-      GFRS_OK)
+  const LaneView lv = view_of(c);
+  if ((rc = upload_ptrs(lv, ptrs.data(), int(ptrs.size()))) != GFRS_OK)
     return rc;
   /* per-idx plan cached in dec_cache keyed off a synthetic mask */
   PlanKey key = plan_key_tag(62); /* EncodeIdx namespace */
   plan_key_set(key, idx);
   DevPlan *p;
-  std::unique_lock<std::mutex> cache_lk(c->cache_mu);
-  auto it = c->dec_cache.find(key);
-  if (it != c->dec_cache.end()) {
-    p = it->second;
-  } else {
-    std::vector<int32_t> in{0};
-    std::vector<int32_t> out(nparity);
-    std::vector<uint8_t> rows(nparity);
-    for (int r = 0; r < nparity; r++) {
-      out[r] = 1 + r;
-      rows[r] = c->enc_matrix[size_t(c->t.n + r) * c->t.n + idx];
-    }
-    p = new DevPlan();
-    rc = p->upload(in, out, rows, c->stream);
-    if (rc != GFRS_OK) {
-      delete p;
-      return rc;
-    }
-    c->dec_cache[key] = p;
-  }
-  launch_rs_apply_xor((const uint64_t *)c->ptr_buf.p, 1 + nparity,
-                      (const int32_t *)p->in_idx.p, 1,
-                      (const int32_t *)p->out_idx.p, p->nout,
-                      (const uint8_t *)p->tabs.p, shard_len, 1, c->stream);
+  auto build = [&](Plan *pl) { return plan_encode_idx(c->code, idx, pl); };
+  rc = cached_plan(c, c->dec_cache, key, c->stream, std::ref(build), &p);
+  if (rc != GFRS_OK) return rc;
+  run_plan(OP_XOR, *p, table_of(lv, 1 + nparity), shard_len, 1, c->stream);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return GFRS_OK;
 }
 
-/* LRC reconstruct+verify in ONE rs_apply_mixed pass: write rows for the
- * bad shards (data, global or local parity, composed over the k global
- * decode inputs), compare rows for every surviving global parity not
- * already an input and every surviving local parity.  Requires the bad
- * set to be globally decodable; returns GFRS_ERR_UNSUPPORTED otherwise
- * so the caller can fall back to local-stripe decode + full verify. */
-static int lrc_mixed_reconstruct_verify(gfrs_ctx_impl *cc, void *base,
-                                        size_t shard_len,
-                                        size_t stripe_stride, int nstripes,
-                                        const int32_t *bad_idx, int nbad,
-                                        uint64_t *fail_bitmap) {
-  const gfrs_tactic &t = cc->t;
-  const int k = t.n, m = t.m;
-  const int total_sh = k + m + t.l;
-  std::vector<uint8_t> present(k + m, 1);
-  std::vector<int> badv(bad_idx, bad_idx + nbad);
-  for (int i = 0; i < nbad; i++) {
-    if (badv[i] < k + m) present[badv[i]] = 0;
-    for (int j = 0; j < i; j++)
-      if (badv[j] == badv[i]) return GFRS_ERR_INVALID_SHARDS;
-  }
-  std::lock_guard<std::mutex> lk(cc->mu);
-  StreamGuard g(cc);
-  PlanKey key = plan_key_tag(60); /* LRC mixed reconstruct+verify */
-  for (int b : badv) plan_key_set(key, b);
-  DevPlan *plan = nullptr;
-  uint32_t cmp_mask = 0;
-  {
-    std::lock_guard<std::mutex> cache_lk(cc->cache_mu);
-    auto it = cc->dec_cache.find(key);
-    if (it != cc->dec_cache.end()) plan = it->second;
-  }
-  /* cmp_mask is derivable from the (cached) row order: rows after nbad
-   * are compares */
-  if (!plan) {
-    std::vector<int> valid;
-    for (int i = 0; i < k + m && int(valid.size()) < k; i++)
-      if (present[i]) valid.push_back(i);
-    if (int(valid.size()) < k) return GFRS_ERR_UNSUPPORTED;
-    std::vector<uint8_t> sub(size_t(k) * k), dec(size_t(k) * k);
-    for (int r = 0; r < k; r++)
-      memcpy(&sub[size_t(r) * k], &cc->enc_matrix[size_t(valid[r]) * k], k);
-    if (!gf_invert(sub.data(), k, dec.data())) return GFRS_ERR_SINGULAR;
-    std::vector<int> slot(k, -1);
-    for (int j = 0; j < k; j++)
-      if (valid[j] < k) slot[valid[j]] = j;
-    const GfTables &gt2 = gft();
-    auto dspace_row = [&](int sh, std::vector<uint8_t> &drow) {
-      drow.assign(k, 0);
-      if (sh < k) {
-        drow[sh] = 1;
-      } else if (sh < k + m) {
-        memcpy(drow.data(), &cc->enc_matrix[size_t(sh) * k], k);
-      } else {
-        const int az = (sh - k - m) / cc->local_m;
-        const int lp = (sh - k - m) % cc->local_m;
-        auto idx = local_stripe(t, az);
-        const uint8_t *lr =
-            &cc->local_matrix[size_t(cc->local_n + lp) * cc->local_n];
-        for (int j = 0; j < cc->local_n; j++) {
-          const int g2i = idx[j];
-          if (g2i < k) {
-            drow[g2i] ^= lr[j];
-          } else {
-            const uint8_t *er = &cc->enc_matrix[size_t(g2i) * k];
-            for (int d = 0; d < k; d++)
-              drow[d] ^= gt2.mul[lr[j]][er[d]];
-          }
-        }
-      }
-    };
-    auto xform = [&](const std::vector<uint8_t> &drow,
-                     std::vector<uint8_t> &row) {
-      row.assign(k, 0);
-      for (int d = 0; d < k; d++) {
-        const uint8_t coef = drow[d];
-        if (!coef) continue;
-        if (present[d]) {
-          row[slot[d]] ^= coef;
-        } else {
-          for (int j = 0; j < k; j++)
-            row[j] ^= gt2.mul[coef][dec[size_t(d) * k + j]];
-        }
-      }
-    };
-    std::vector<int32_t> in, out;
-    std::vector<uint8_t> rows, row, drow;
-    for (int j = 0; j < k; j++) in.push_back(valid[j]);
-    for (int b : badv) { /* write rows */
-      out.push_back(b);
-      dspace_row(b, drow);
-      xform(drow, row);
-      rows.insert(rows.end(), row.begin(), row.end());
-    }
-    auto add_check = [&](int sh) {
-      out.push_back(sh);
-      dspace_row(sh, drow);
-      xform(drow, row);
-      rows.insert(rows.end(), row.begin(), row.end());
-    };
-    for (int p2 = k; p2 < k + m; p2++) {
-      if (!present[p2]) continue;
-      if (std::find(valid.begin(), valid.end(), p2) != valid.end()) continue;
-      add_check(p2);
-    }
-    for (int q = k + m; q < total_sh; q++)
-      if (std::find(badv.begin(), badv.end(), q) == badv.end())
-        add_check(q);
-    if (out.size() > 32) return GFRS_ERR_UNSUPPORTED; /* cmp_mask width */
-    plan = new DevPlan();
-    int rc = plan->upload(in, out, rows, cc->stream, k);
-    if (rc != GFRS_OK) {
-      delete plan;
-      return rc;
-    }
-    {
-      std::lock_guard<std::mutex> cache_lk(cc->cache_mu);
-      cc->dec_cache[key] = plan;
-    }
-  }
-  for (int r = nbad; r < plan->nout; r++) cmp_mask |= 1u << r;
-  int rc;
-  if ((rc = cc->fail_buf.ensure(size_t(nstripes) * 4)) != GFRS_OK) return rc;
-  HIP_TRY(hipMemsetAsync(cc->fail_buf.p, 0, size_t(nstripes) * 4,
-                         cc->stream));
-  launch_rs_apply_mixed_strided((uint64_t)base, stripe_stride,
-                                (const int32_t *)plan->in_idx.p, plan->k,
-                                (const int32_t *)plan->out_idx.p, plan->nout,
-                                (const uint8_t *)plan->tabs.p, cmp_mask,
-                                shard_len, nstripes,
-                                (uint32_t *)cc->fail_buf.p, cc->stream);
-  std::vector<uint32_t> fails(nstripes);
-  HIP_TRY(hipMemcpyAsync(fails.data(), cc->fail_buf.p, size_t(nstripes) * 4,
-                         hipMemcpyDeviceToHost, cc->stream));
-  HIP_TRY(hipStreamSynchronize(cc->stream));
-  if (fail_bitmap) {
-    memset(fail_bitmap, 0, ((nstripes + 63) / 64) * 8);
-    for (int s2 = 0; s2 < nstripes; s2++)
-      if (fails[s2]) fail_bitmap[s2 / 64] |= 1ull << (s2 % 64);
-  }
-  return GFRS_OK;
+/* Reconstruct + verify in ONE rs_apply_mixed pass over a plan that writes
+ * the bad shards and compares surviving parities (gfrs_plan.h has the row
+ * conventions of both builders):
+ *   plain RS (tag 63): duplicates in the bad list are tolerated;
+ *   LRC (tag 60): every bad shard - data, global or local parity - is a
+ *     write row composed over the k global decode inputs.  Requires the bad
+ *     set to be globally decodable; returns GFRS_ERR_UNSUPPORTED otherwise
+ *     so the caller can fall back to local-stripe decode + full verify. */
+static int reconstruct_verify_mixed(gfrs_ctx_impl *c, void *base,
+                                    size_t shard_len, size_t stripe_stride,
+                                    int nstripes, const int32_t *bad_idx,
+                                    int nbad, uint64_t *fail_bitmap) {
+  const bool lrc = c->code.t.l != 0;
+  PlanKey key;
+  int rc = bad_list_key(lrc ? 60 : 63, bad_idx, nbad, c->code.total,
+                        /*dup_ok=*/!lrc, &key);
+  if (rc != GFRS_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+  DevPlan *plan;
+  auto build = [&](Plan *pl) {
+    return (lrc ? plan_lrc_reconstruct_verify
+                : plan_rs_reconstruct_verify)(c->code, bad_idx, nbad, pl);
+  };
+  rc = cached_plan(c, c->dec_cache, key, c->stream, std::ref(build), &plan);
+  if (rc != GFRS_OK) return rc;
+  if ((rc = fail_begin(&c->fail_buf, nstripes, c->stream)) != GFRS_OK)
+    return rc;
+  run_plan(OP_MIXED, *plan, strided(base, stripe_stride), shard_len, nstripes,
+           c->stream, (uint32_t *)c->fail_buf.p);
+  return fail_finish(&c->fail_buf, nstripes, c->stream, fail_bitmap);
 }
 
 int gfrs_reconstruct_verify_batch(gfrs_ctx *ctx, void *base,
@@ -1505,132 +1274,30 @@ int gfrs_reconstruct_verify_batch(gfrs_ctx *ctx, void *base,
                                   int nstripes, const int32_t *bad_idx,
                                   int nbad, uint64_t *fail_bitmap) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  const gfrs_tactic &t = c->t;
+  const gfrs_tactic &t = c->code.t;
   if (nstripes <= 0) return GFRS_ERR_INVALID_SHARDS;
-  if (t.l != 0) {
-    /* LRC single pass: every bad shard (data, global or local parity)
-     * is a write row composed over the k global-decode inputs, and
-     * every surviving global/local parity is a compare row - ONE
-     * rs_apply_mixed pass instead of reconstruct + full re-read verify.
-     * Falls back to two passes only when the bad set needs local-stripe
-     * decode (globally undecodable). */
-    int nglobad = 0;
-    bool ok_range = true;
-    for (int i = 0; i < nbad; i++) {
-      if (bad_idx[i] < 0 || bad_idx[i] >= t.n + t.m + t.l) ok_range = false;
-      else if (bad_idx[i] < t.n + t.m) nglobad++;
-    }
-    if (!ok_range) return GFRS_ERR_INVALID_SHARDS;
-    if (nglobad <= t.m && c->fused_lrc_ok) {
-      int rc = lrc_mixed_reconstruct_verify(c, base, shard_len,
-                                            stripe_stride, nstripes,
-                                            bad_idx, nbad, fail_bitmap);
-      if (rc != GFRS_ERR_UNSUPPORTED) return rc;
-    }
-    int rc = gfrs_reconstruct_batch(ctx, base, shard_len, stripe_stride,
-                                    nstripes, bad_idx, nbad, 0);
-    if (rc != GFRS_OK) return rc;
-    return gfrs_verify_batch(ctx, base, shard_len, stripe_stride, nstripes,
-                             fail_bitmap);
-  }
-  const int k = t.n, m = t.m;
-  std::vector<uint8_t> present(k + m, 1);
+  if (t.l == 0)
+    return reconstruct_verify_mixed(c, base, shard_len, stripe_stride,
+                                    nstripes, bad_idx, nbad, fail_bitmap);
+  /* LRC single pass: ONE rs_apply_mixed pass instead of reconstruct + full
+   * re-read verify.  Falls back to two passes only when the bad set needs
+   * local-stripe decode (globally undecodable). */
+  int nglobad = 0;
   for (int i = 0; i < nbad; i++) {
-    if (bad_idx[i] < 0 || bad_idx[i] >= k + m) return GFRS_ERR_INVALID_SHARDS;
-    present[bad_idx[i]] = 0;
+    if (bad_idx[i] < 0 || bad_idx[i] >= c->code.total)
+      return GFRS_ERR_INVALID_SHARDS;
+    if (bad_idx[i] < t.n + t.m) nglobad++;
   }
-  std::lock_guard<std::mutex> lk(c->mu);
-  StreamGuard g(c);
-
-  PlanKey key = plan_key_tag(63); /* reconstruct+verify namespace */
-  for (int i = 0; i < k + m; i++)
-    if (!present[i]) plan_key_set(key, i);
-  DevPlan *plan = nullptr;
-  uint32_t cmp_mask = 0;
-  {
-    std::lock_guard<std::mutex> cache_lk(c->cache_mu);
-    auto it = c->dec_cache.find(key);
-    if (it != c->dec_cache.end()) plan = it->second;
+  if (nglobad <= t.m && c->fused_lrc_ok) {
+    int rc = reconstruct_verify_mixed(c, base, shard_len, stripe_stride,
+                                      nstripes, bad_idx, nbad, fail_bitmap);
+    if (rc != GFRS_ERR_UNSUPPORTED) return rc;
   }
-  if (!plan) {
-    /* valid inputs: first k present in index order (reedsolomon.go:1453) */
-    std::vector<int> valid;
-    for (int i = 0; i < k + m && int(valid.size()) < k; i++)
-      if (present[i]) valid.push_back(i);
-    if (int(valid.size()) < k) return GFRS_ERR_TOO_FEW_SHARDS;
-    std::vector<uint8_t> sub(size_t(k) * k), dec(size_t(k) * k);
-    for (int r = 0; r < k; r++)
-      memcpy(&sub[size_t(r) * k], &c->enc_matrix[size_t(valid[r]) * k], k);
-    if (!gf_invert(sub.data(), k, dec.data())) return GFRS_ERR_SINGULAR;
-    /* input slot of each present data column */
-    std::vector<int> slot(k, -1);
-    for (int j = 0; j < k; j++)
-      if (valid[j] < k) slot[valid[j]] = j;
-
-    const GfTables &gt2 = gft();
-    std::vector<int32_t> in, out;
-    std::vector<uint8_t> rows;
-    for (int j = 0; j < k; j++) in.push_back(valid[j]);
-    /* 1) missing data: decode rows (write) */
-    for (int i = 0; i < k; i++)
-      if (!present[i]) {
-        out.push_back(i);
-        rows.insert(rows.end(), &dec[size_t(i) * k], &dec[size_t(i) * k + k]);
-      }
-    /* 2) every parity row composed over the valid inputs:
-     *    ver_p[j] = enc_p[d]·1[slot(d)==j] (+) Σ_missing enc_p[d]·dec[d][j] */
-    for (int p2 = k; p2 < k + m; p2++) {
-      std::vector<uint8_t> row(k, 0);
-      for (int d = 0; d < k; d++) {
-        const uint8_t coef = c->enc_matrix[size_t(p2) * k + d];
-        if (present[d]) {
-          row[slot[d]] ^= coef;
-        } else {
-          for (int j = 0; j < k; j++)
-            row[j] ^= gt2.mul[coef][dec[size_t(d) * k + j]];
-        }
-      }
-      out.push_back(p2);
-      rows.insert(rows.end(), row.begin(), row.end());
-    }
-    plan = new DevPlan();
-    int rc = plan->upload(in, out, rows, c->stream);
-    if (rc != GFRS_OK) {
-      delete plan;
-      return rc;
-    }
-    {
-      std::lock_guard<std::mutex> cache_lk(c->cache_mu);
-      c->dec_cache[key] = plan;
-    }
-  }
-  /* compare bits: present parity rows; missing (data or parity) written */
-  {
-    int nmissdata = 0;
-    for (int i = 0; i < k; i++)
-      if (!present[i]) nmissdata++;
-    for (int p2 = k; p2 < k + m; p2++)
-      if (present[p2]) cmp_mask |= 1u << (nmissdata + (p2 - k));
-  }
-  int rc;
-  if ((rc = c->fail_buf.ensure(size_t(nstripes) * 4)) != GFRS_OK) return rc;
-  HIP_TRY(hipMemsetAsync(c->fail_buf.p, 0, size_t(nstripes) * 4, c->stream));
-  launch_rs_apply_mixed_strided((uint64_t)base, stripe_stride,
-                                (const int32_t *)plan->in_idx.p, plan->k,
-                                (const int32_t *)plan->out_idx.p, plan->nout,
-                                (const uint8_t *)plan->tabs.p, cmp_mask,
-                                shard_len, nstripes,
-                                (uint32_t *)c->fail_buf.p, c->stream);
-  std::vector<uint32_t> fails(nstripes);
-  HIP_TRY(hipMemcpyAsync(fails.data(), c->fail_buf.p, size_t(nstripes) * 4,
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (fail_bitmap) {
-    memset(fail_bitmap, 0, ((nstripes + 63) / 64) * 8);
-    for (int s2 = 0; s2 < nstripes; s2++)
-      if (fails[s2]) fail_bitmap[s2 / 64] |= 1ull << (s2 % 64);
-  }
-  return GFRS_OK;
+  int rc = gfrs_reconstruct_batch(ctx, base, shard_len, stripe_stride,
+                                  nstripes, bad_idx, nbad, 0);
+  if (rc != GFRS_OK) return rc;
+  return gfrs_verify_batch(ctx, base, shard_len, stripe_stride, nstripes,
+                           fail_bitmap);
 }
 
 int gfrs_update_idx(gfrs_ctx *ctx, const void *old_shard,
@@ -1641,6 +1308,95 @@ int gfrs_update_idx(gfrs_ctx *ctx, const void *old_shard,
   return gfrs_encode_idx(ctx, new_shard, idx, parity, shard_len, nparity);
 }
 
+/* Chunked finalize pipeline (GFRS_REPAIR_CHUNK=N, DEFAULT OFF): stripes
+ * per chunk, nstripes = one launch.  The header/footer pass of chunk c only
+ * needs chunk c's images (the footer CRC is GF(2)-combined from the frame
+ * CRCs the repair kernel just wrote), so it can run on an aux stream behind
+ * an event while chunk c+1's repair kernel streams on the main stream.
+ * Measured @512x4MiB RS(6+3) bad=[2,6]: the single launch wins — 5.66 ms
+ * serial vs 6.48-7.71 chunked (CH=64/128/256): each repair sub-launch pays
+ * a fill/drain ramp and the finalize competes for bandwidth, costing more
+ * than the ~0.9 ms finalize pass hides.  Kept as a measured variant;
+ * parity-tested (test_repair_batch_chunk_pipeline). */
+static int repair_chunk(size_t shard_len, int nstripes) {
+  if (shard_len <= 4096) return nstripes;
+  const char *e = getenv("GFRS_REPAIR_CHUNK");
+  const long v = e ? atol(e) : 0;
+  return v > 0 && v < (long)nstripes ? (int)v : nstripes;
+}
+
+/* Fused repair: one kernel reads the k inputs + surviving-parity check
+ * shards and writes ONLY the repaired shards' framed bodies - the raw
+ * reconstruction never touches HBM and `base` is NOT mutated (the legacy
+ * path of gfrs_repair_batch reconstructs in place). */
+static int repair_fused(gfrs_ctx_impl *cc, void *base, size_t shard_len,
+                        size_t stripe_stride, int nstripes,
+                        const int32_t *bad_idx, int nbad, void *disk_dst,
+                        size_t dst_stride, int64_t block_len,
+                        const uint64_t *bids, const uint64_t *vuids,
+                        uint64_t *fail_bitmap) {
+  /* the image column of each rebuild row follows the caller's order, which
+   * the cached plan (keyed by the bad SET, local-parity bads included)
+   * does not know */
+  uint32_t colpack = 0;
+  PlanKey key; /* 61 = fused-repair namespace */
+  int rc = bad_list_key(61, bad_idx, nbad, cc->code.total, /*dup_ok=*/false,
+                        &key);
+  if (rc == GFRS_OK)
+    rc = repair_colpack(cc->code.total, bad_idx, nbad, &colpack);
+  if (rc != GFRS_OK) return rc;
+  std::lock_guard<std::mutex> lk(cc->mu);
+  StreamGuard g(cc);
+  DevPlan *plan;
+  auto build = [&](Plan *pl) {
+    return plan_fused_repair(cc->code, bad_idx, nbad, pl);
+  };
+  rc = cached_plan(cc, cc->dec_cache, key, cc->stream, std::ref(build), &plan);
+  if (rc != GFRS_OK) return rc;
+  if ((rc = fail_begin(&cc->fail_buf, nstripes, cc->stream)) != GFRS_OK)
+    return rc;
+  uint32_t *fail = (uint32_t *)cc->fail_buf.p;
+  /* id arrays for every (stripe, bad) image, caller's column order;
+   * headers themselves are built by the finalize kernel */
+  const size_t nimg = size_t(nstripes) * nbad;
+  if ((rc = stage_ids(cc, bids, vuids, nimg)) != GFRS_OK) return rc;
+  const uint64_t *ids = (const uint64_t *)cc->ptr_buf.p;
+  /* stripes [lo, lo+cn): repair kernel on the main stream, then the
+   * header/footer pass on `fin` */
+  auto repair = [&](int lo, int cn, hipStream_t fin, hipEvent_t ev) {
+    uint8_t *cd = (uint8_t *)disk_dst + size_t(lo) * nbad * dst_stride;
+    (shard_len <= 4096 ? launch_rs_repair_frame_small
+                       : launch_rs_repair_frame)(
+        cd + 32, dst_stride, (uint64_t)base + (uint64_t)lo * stripe_stride,
+        stripe_stride, shard_len, plan->k, plan->nout, nbad, plan->in(),
+        plan->tab(), colpack, fail + lo, cn, cc->stream);
+    if (ev) {
+      HIP_TRY(hipEventRecord(ev, cc->stream));
+      HIP_TRY(hipStreamWaitEvent(fin, ev, 0));
+    }
+    launch_shard_finalize(cd, dst_stride, ids + size_t(lo) * nbad,
+                          ids + nimg + size_t(lo) * nbad, int64_t(shard_len),
+                          block_len, cn * nbad, fin);
+    return int(GFRS_OK);
+  };
+  const int chunk = repair_chunk(shard_len, nstripes);
+  const bool pipe = chunk < nstripes && cc->ensure_aux() == GFRS_OK;
+  if (!pipe) {
+    repair(0, nstripes, cc->stream, nullptr);
+  } else {
+    int ci = 0;
+    for (int lo = 0; lo < nstripes; lo += chunk, ci++)
+      if ((rc = repair(lo, std::min(chunk, nstripes - lo), cc->aux_stream,
+                       cc->aux_ev[ci & 1])) != GFRS_OK)
+        return rc;
+    HIP_TRY(hipEventRecord(cc->aux_done, cc->aux_stream));
+    HIP_TRY(hipStreamWaitEvent(cc->stream, cc->aux_done, 0));
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("repair_frame launch", e);
+  return fail_finish(&cc->fail_buf, nstripes, cc->stream, fail_bitmap);
+}
+
 int gfrs_repair_batch(gfrs_ctx *ctx, void *base, size_t shard_len,
                       size_t stripe_stride, int nstripes,
                       const int32_t *bad_idx, int nbad, void *disk_dst,
@@ -1649,254 +1405,26 @@ int gfrs_repair_batch(gfrs_ctx *ctx, void *base, size_t shard_len,
                       uint64_t *fail_bitmap) {
   if (nbad <= 0) return GFRS_ERR_INVALID_SHARDS;
   auto *cc = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  {
-    const gfrs_tactic &t = cc->t;
-    /* Fused repair: one kernel reads the k inputs + surviving-parity
-     * check shards and writes ONLY the repaired shards' framed bodies -
-     * the raw reconstruction never touches HBM and `base` is NOT
-     * mutated (the legacy path below reconstructs in place). */
-    static const size_t fmin = []() {
-      const char *e = getenv("GFRS_FUSED_MIN");
-      const long v = e ? atol(e) : 0;
-      return v > 0 ? size_t(v) : size_t(4097);
-    }();
-    int nglobad = 0;
-    for (int i = 0; i < nbad; i++)
-      if (bad_idx[i] < t.n + t.m) nglobad++;
-    /* The kernel carries 4 rows: nbad rebuild rows plus one check row per
-     * surviving parity that is not an input, m + l rows in all.  A tactic
-     * with m + l > 4 (RS(6+6)) would drop check rows and pass stripes the
-     * reference Verify fails, so it takes the legacy path. */
-    if ((t.l == 0 || cc->fused_lrc_ok) && block_len == 65536 && t.m >= 1 &&
-        t.m + t.l <= 4 && t.n + t.m + t.l <= 16 && nglobad <= t.m &&
-        nbad <= 4 &&
-        (shard_len >= fmin || shard_len <= 4096) && dst_stride % 4 == 0 &&
-        nstripes > 0) {
-      const int k = t.n, m = t.m;
-      const int total_sh = k + m + t.l;
-      std::vector<uint8_t> present(k + m, 1);
-      std::vector<int> badv(bad_idx, bad_idx + nbad);
-      bool badrange = false;
-      for (int i = 0; i < nbad; i++) {
-        if (badv[i] < 0 || badv[i] >= total_sh) return GFRS_ERR_INVALID_SHARDS;
-        if (badv[i] < k + m) present[badv[i]] = 0;
-        for (int j = 0; j < i; j++)
-          if (badv[j] == badv[i]) badrange = true;
-      }
-      if (badrange) return GFRS_ERR_INVALID_SHARDS;
-      std::vector<int> sbad = badv;
-      std::sort(sbad.begin(), sbad.end());
-      uint32_t colpack = 0;
-      for (int r = 0; r < nbad; r++) {
-        int col = int(std::find(badv.begin(), badv.end(), sbad[r]) -
-                      badv.begin());
-        colpack |= uint32_t(col) << (4 * r);
-      }
-      std::lock_guard<std::mutex> lk(cc->mu);
-      StreamGuard g(cc);
-      PlanKey key = plan_key_tag(61); /* fused-repair namespace */
-      for (int b : badv) plan_key_set(key, b); /* incl. local-parity bads */
-      DevPlan *plan = nullptr;
-      {
-        std::lock_guard<std::mutex> cache_lk(cc->cache_mu);
-        auto it = cc->dec_cache.find(key);
-        if (it != cc->dec_cache.end()) plan = it->second;
-      }
-      if (!plan) {
-        std::vector<int> valid;
-        for (int i = 0; i < k + m && int(valid.size()) < k; i++)
-          if (present[i]) valid.push_back(i);
-        if (int(valid.size()) < k) return GFRS_ERR_TOO_FEW_SHARDS;
-        std::vector<uint8_t> sub(size_t(k) * k), dec(size_t(k) * k);
-        for (int r = 0; r < k; r++)
-          memcpy(&sub[size_t(r) * k], &cc->enc_matrix[size_t(valid[r]) * k],
-                 k);
-        if (!gf_invert(sub.data(), k, dec.data()))
-          return GFRS_ERR_SINGULAR;
-        std::vector<int> slot(k, -1);
-        for (int j = 0; j < k; j++)
-          if (valid[j] < k) slot[valid[j]] = j;
-        const GfTables &gt2 = gft();
-        /* shard idx -> its row over the n data shards (locals compose
-         * through the global-parity rows, as in the fused_lrc plan) */
-        auto dspace_row = [&](int sh, std::vector<uint8_t> &drow) {
-          drow.assign(k, 0);
-          if (sh < k) {
-            drow[sh] = 1;
-          } else if (sh < k + m) {
-            memcpy(drow.data(), &cc->enc_matrix[size_t(sh) * k], k);
-          } else {
-            const int az = (sh - k - m) / cc->local_m;
-            const int lp = (sh - k - m) % cc->local_m;
-            auto idx = local_stripe(t, az);
-            const uint8_t *lr =
-                &cc->local_matrix[size_t(cc->local_n + lp) * cc->local_n];
-            for (int j = 0; j < cc->local_n; j++) {
-              const int g2i = idx[j];
-              if (g2i < k) {
-                drow[g2i] ^= lr[j];
-              } else {
-                const uint8_t *er = &cc->enc_matrix[size_t(g2i) * k];
-                for (int d = 0; d < k; d++)
-                  drow[d] ^= gt2.mul[lr[j]][er[d]];
-              }
-            }
-          }
-        };
-        /* data-space row -> row over the k chosen inputs */
-        auto xform = [&](const std::vector<uint8_t> &drow,
-                         std::vector<uint8_t> &row) {
-          row.assign(k, 0);
-          for (int d = 0; d < k; d++) {
-            const uint8_t coef = drow[d];
-            if (!coef) continue;
-            if (present[d]) {
-              row[slot[d]] ^= coef;
-            } else {
-              for (int j = 0; j < k; j++)
-                row[j] ^= gt2.mul[coef][dec[size_t(d) * k + j]];
-            }
-          }
-        };
-        std::vector<int32_t> in, out;
-        std::vector<uint8_t> rows, row, drow;
-        for (int j = 0; j < k; j++) in.push_back(valid[j]);
-        /* rebuild rows in sorted-bad order (data, global or local) */
-        for (int b : sbad) {
-          out.push_back(b);
-          dspace_row(b, drow);
-          xform(drow, row);
-          rows.insert(rows.end(), row.begin(), row.end());
-        }
-        /* check rows while they fit in the 4-row kernel budget:
-         * surviving globals not already inputs, then surviving locals
-         * (the locals restore detection when npresent == k globally) */
-        auto add_check = [&](int sh) {
-          if (int(out.size()) >= 4) return;
-          out.push_back(sh);
-          dspace_row(sh, drow);
-          xform(drow, row);
-          rows.insert(rows.end(), row.begin(), row.end());
-          in.push_back(sh); /* cmp shard index rides after the k inputs */
-        };
-        for (int p2 = k; p2 < k + m; p2++) {
-          if (!present[p2]) continue;
-          if (std::find(valid.begin(), valid.end(), p2) != valid.end())
-            continue; /* input parity: its check is the identity */
-          add_check(p2);
-        }
-        for (int q = k + m; q < total_sh; q++)
-          if (std::find(badv.begin(), badv.end(), q) == badv.end())
-            add_check(q);
-        plan = new DevPlan();
-        int rc2 = plan->upload(in, out, rows, cc->stream, k);
-        if (rc2 != GFRS_OK) {
-          delete plan;
-          return rc2;
-        }
-        {
-          std::lock_guard<std::mutex> cache_lk(cc->cache_mu);
-          cc->dec_cache[key] = plan;
-        }
-      }
-      const int gm = plan->nout;
-      int rc2;
-      if ((rc2 = cc->fail_buf.ensure(size_t(nstripes) * 4)) != GFRS_OK)
-        return rc2;
-      HIP_TRY(hipMemsetAsync(cc->fail_buf.p, 0, size_t(nstripes) * 4,
-                             cc->stream));
-      /* id arrays for every (stripe, bad) image, caller's column order;
-       * headers themselves are built by the finalize kernel */
-      const size_t nimg = size_t(nstripes) * nbad, idbytes = nimg * 8;
-      if (cc->ids_pending) { /* a queued gfrs_shard_write_batch upload */
-        HIP_TRY(hipEventSynchronize(cc->ids_ev));
-        cc->ids_pending = false;
-      }
-      if ((rc2 = cc->stage_pin.ensure(idbytes * 2)) != GFRS_OK) return rc2;
-      memcpy(cc->stage_pin.p, bids, idbytes);
-      memcpy((uint8_t *)cc->stage_pin.p + idbytes, vuids, idbytes);
-      DevBuf &hbuf = cc->ptr_buf;
-      if ((rc2 = hbuf.ensure(idbytes * 2)) != GFRS_OK) return rc2;
-      HIP_TRY(hipMemcpyAsync(hbuf.p, cc->stage_pin.p, idbytes * 2,
-                             hipMemcpyHostToDevice, cc->stream));
-      /* Chunked finalize pipeline (GFRS_REPAIR_CHUNK=N, DEFAULT OFF):
-       * the header/footer pass of chunk c only needs chunk c's images
-       * (the footer CRC is GF(2)-combined from the frame CRCs the
-       * repair kernel just wrote), so it can run on an aux stream
-       * behind an event while chunk c+1's repair kernel streams on the
-       * main stream.  Measured @512x4MiB RS(6+3) bad=[2,6]: the single
-       * launch wins — 5.66 ms serial vs 6.48-7.71 chunked (CH=64/128/
-       * 256): each repair sub-launch pays a fill/drain ramp and the
-       * finalize competes for bandwidth, costing more than the ~0.9 ms
-       * finalize pass hides.  Kept as a measured variant; parity-tested
-       * (test_repair_batch_chunk_pipeline). */
-      int chunk = nstripes;
-      if (shard_len > 4096) {
-        const char *e = getenv("GFRS_REPAIR_CHUNK");
-        const long v = e ? atol(e) : 0;
-        if (v > 0 && v < (long)nstripes) chunk = (int)v;
-      }
-      const bool pipe = chunk < nstripes && cc->ensure_aux() == GFRS_OK;
-      if (!pipe) {
-        if (shard_len <= 4096)
-          launch_rs_repair_frame_small((uint8_t *)disk_dst + 32, dst_stride,
-                                       (uint64_t)base, stripe_stride,
-                                       shard_len, plan->k, gm, nbad,
-                                       (const int32_t *)plan->in_idx.p,
-                                       (const uint8_t *)plan->tabs.p,
-                                       colpack, (uint32_t *)cc->fail_buf.p,
-                                       nstripes, cc->stream);
-        else
-          launch_rs_repair_frame((uint8_t *)disk_dst + 32, dst_stride,
-                                 (uint64_t)base, stripe_stride, shard_len,
-                                 plan->k, gm, nbad,
-                                 (const int32_t *)plan->in_idx.p,
-                                 (const uint8_t *)plan->tabs.p, colpack,
-                                 (uint32_t *)cc->fail_buf.p, nstripes,
-                                 cc->stream);
-        launch_shard_finalize((uint8_t *)disk_dst, dst_stride,
-                              (const uint64_t *)hbuf.p,
-                              (const uint64_t *)hbuf.p + nimg,
-                              int64_t(shard_len), block_len, nstripes * nbad,
-                              cc->stream);
-      } else {
-        int ci = 0;
-        for (int lo = 0; lo < nstripes; lo += chunk, ci++) {
-          const int cn = std::min(chunk, nstripes - lo);
-          uint8_t *cd =
-              (uint8_t *)disk_dst + size_t(lo) * nbad * dst_stride;
-          launch_rs_repair_frame(
-              cd + 32, dst_stride,
-              (uint64_t)base + (uint64_t)lo * stripe_stride, stripe_stride,
-              shard_len, plan->k, gm, nbad, (const int32_t *)plan->in_idx.p,
-              (const uint8_t *)plan->tabs.p, colpack,
-              (uint32_t *)cc->fail_buf.p + lo, cn, cc->stream);
-          hipEvent_t ev = cc->aux_ev[ci & 1];
-          HIP_TRY(hipEventRecord(ev, cc->stream));
-          HIP_TRY(hipStreamWaitEvent(cc->aux_stream, ev, 0));
-          launch_shard_finalize(
-              cd, dst_stride, (const uint64_t *)hbuf.p + size_t(lo) * nbad,
-              (const uint64_t *)hbuf.p + nimg + size_t(lo) * nbad,
-              int64_t(shard_len), block_len, cn * nbad, cc->aux_stream);
-        }
-        HIP_TRY(hipEventRecord(cc->aux_done, cc->aux_stream));
-        HIP_TRY(hipStreamWaitEvent(cc->stream, cc->aux_done, 0));
-      }
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail("repair_frame launch", e);
-      std::vector<uint32_t> fails(nstripes);
-      HIP_TRY(hipMemcpyAsync(fails.data(), cc->fail_buf.p,
-                             size_t(nstripes) * 4, hipMemcpyDeviceToHost,
-                             cc->stream));
-      HIP_TRY(hipStreamSynchronize(cc->stream));
-      if (fail_bitmap) {
-        memset(fail_bitmap, 0, ((nstripes + 63) / 64) * 8);
-        for (int s2 = 0; s2 < nstripes; s2++)
-          if (fails[s2]) fail_bitmap[s2 / 64] |= 1ull << (s2 % 64);
-      }
-      return GFRS_OK;
-    }
-  }
+  const gfrs_tactic &t = cc->code.t;
+  static const size_t fmin = []() {
+    const char *e = getenv("GFRS_FUSED_MIN");
+    const long v = e ? atol(e) : 0;
+    return v > 0 ? size_t(v) : size_t(4097);
+  }();
+  int nglobad = 0;
+  for (int i = 0; i < nbad; i++)
+    if (bad_idx[i] < t.n + t.m) nglobad++;
+  /* The kernel carries 4 rows: nbad rebuild rows plus one check row per
+   * surviving parity that is not an input, m + l rows in all.  A tactic
+   * with m + l > 4 (RS(6+6)) would drop check rows and pass stripes the
+   * reference Verify fails, so it takes the legacy path. */
+  if ((t.l == 0 || cc->fused_lrc_ok) && block_len == 65536 && t.m >= 1 &&
+      t.m + t.l <= 4 && t.n + t.m + t.l <= 16 && nglobad <= t.m &&
+      nbad <= 4 && (shard_len >= fmin || shard_len <= 4096) &&
+      dst_stride % 4 == 0 && nstripes > 0)
+    return repair_fused(cc, base, shard_len, stripe_stride, nstripes, bad_idx,
+                        nbad, disk_dst, dst_stride, block_len, bids, vuids,
+                        fail_bitmap);
   /* legacy path: reconstruct + the mandatory verify in one data pass */
   int rc = gfrs_reconstruct_verify_batch(ctx, base, shard_len, stripe_stride,
                                          nstripes, bad_idx, nbad,

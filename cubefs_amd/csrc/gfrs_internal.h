@@ -1,5 +1,6 @@
 /* cubefs_amd/csrc/gfrs_internal.h — internal declarations shared between
  * the host runtime (gfrs_host.cpp) and kernel launchers (gfrs_kernels.hip).
+ * The GF(2^8) math and the plan builders are in gfrs_plan.h (no HIP).
  * Product code: independent of oracle/.
  */
 #ifndef GFRS_INTERNAL_H
@@ -11,28 +12,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gfrs_plan.h"
+
 namespace gfrs {
-
-/* ---- GF(2^8) field, poly 0x11D (generator 29; galois.go:25) ---- */
-struct GfTables {
-  uint8_t log_t[256];
-  uint8_t exp_t[510];
-  uint8_t mul[256][256];
-  /* nibble tables: lo[c][x] = mul[c][x], hi[c][x] = mul[c][x<<4]
-   * (galois.go:340,596) */
-  uint8_t lo[256][16];
-  uint8_t hi[256][16];
-  GfTables();
-  uint8_t gexp(uint8_t a, int n) const; /* galois.go:892 */
-  uint8_t div(uint8_t a, uint8_t b) const;
-};
-const GfTables &gft();
-
-/* Row-major byte matrix helpers (matrix.go). */
-bool gf_invert(const uint8_t *in, int n, uint8_t *out); /* false = singular */
-/* klauspost default encode matrix: vandermonde(total,k) × inv(top k×k)
- * (reedsolomon.go:220-244).  out is total×k. */
-bool gf_build_matrix(int k, int total, uint8_t *out);
 
 /* ---- kernel launch interface ---- */
 
@@ -42,7 +24,8 @@ bool gf_build_matrix(int k, int total, uint8_t *out);
  * where in/out shard pointers come from ptrs[s*nptr + idx]:
  *   in  c -> ptrs[s*nptr + in_idx[c]]
  *   out r -> ptrs[s*nptr + out_idx[r]]
- * tabs = device array [nout*k][32]: per-coefficient lo|hi nibble tables.
+ * tabs = device array [nout*k][32]: per-coefficient A|B|C linear-split
+ * tables (DevPlan::upload in gfrs_host.cpp documents the layout).
  * All index/table arrays are device memory. */
 void launch_rs_apply(const uint64_t *ptrs, int nptr, const int32_t *in_idx,
                      int k, const int32_t *out_idx, int nout,

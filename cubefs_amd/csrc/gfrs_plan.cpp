@@ -1,0 +1,329 @@
+/* cubefs_amd/csrc/gfrs_plan.cpp — coding-plan construction (see
+ * gfrs_plan.h).  One copy of each piece of algebra:
+ *   dspace_row   shard index -> its row over the n data shards
+ *   Basis        the first k present shards, inverted
+ *   over_inputs  data-space row -> row over the k chosen inputs
+ * Every builder is a few lines on top of them.  A row that expresses
+ * out[r] over k independent inputs is unique, so the builders only have to
+ * agree on `in` and `out`.
+ */
+#include "gfrs_plan.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace gfrs {
+
+bool tactic_valid(const gfrs_tactic *t) {
+  /* codemode.go:291-299 IsValid; replicate modes (m==0, l==0) are legal —
+   * ec.NewEncoder accepts them and Encode is a no-op (reedsolomon.go:442) */
+  if (!t) return false;
+  if (t->m == 0 && t->l == 0)
+    return t->n > 0 && t->az_count > 0 && t->n % t->az_count == 0;
+  if (t->n <= 0 || t->m <= 0 || t->l < 0 || t->az_count <= 0) return false;
+  if (t->n % t->az_count || t->m % t->az_count || t->l % t->az_count)
+    return false;
+  if (t->n + t->m > 256) return false;
+  if (t->l > 0 && (t->n + t->m) / t->az_count + t->l / t->az_count > 256)
+    return false;
+  return true;
+}
+
+bool code_build(const gfrs_tactic &t, Code *c) {
+  c->t = t;
+  c->total = t.n + t.m + t.l;
+  /* global encode matrix (reedsolomon.go:220-244); replicate modes have
+   * no parity engine (reedsolomon.go:442 parityShards==0 early return) */
+  if (t.m > 0) {
+    c->enc_matrix.resize(size_t(t.n + t.m) * t.n);
+    if (!gf_build_matrix(t.n, t.n + t.m, c->enc_matrix.data())) return false;
+  }
+  /* local engines (encoder.go:92-104) */
+  if (t.l > 0) {
+    c->local_n = (t.n + t.m) / t.az_count;
+    c->local_m = t.l / t.az_count;
+    c->local_matrix.resize(size_t(c->local_n + c->local_m) * c->local_n);
+    if (!gf_build_matrix(c->local_n, c->local_n + c->local_m,
+                         c->local_matrix.data()))
+      return false;
+  }
+  return true;
+}
+
+std::vector<int32_t> local_stripe(const gfrs_tactic &t, int az_idx) {
+  int ln = t.n / t.az_count, lm = t.m / t.az_count, ll = t.l / t.az_count;
+  std::vector<int32_t> idx;
+  idx.reserve(ln + lm + ll);
+  for (int i = 0; i < ln; i++) idx.push_back(az_idx * ln + i);
+  for (int i = 0; i < lm; i++) idx.push_back(t.n + az_idx * lm + i);
+  for (int i = 0; i < ll; i++) idx.push_back(t.n + t.m + az_idx * ll + i);
+  return idx;
+}
+
+/* Shard index -> its row over the n data shards.  Data and global parity
+ * shards are rows of the encode matrix (whose top is the identity).  A
+ * local parity is linear in its local stripe: an input that is a data
+ * shard contributes its coefficient directly; one that is a global parity
+ * contributes localcoef x its parity row (GF linearity). */
+static void dspace_row(const Code &c, int sh, uint8_t *drow) {
+  const int k = c.t.n, m = c.t.m;
+  if (sh < k + m) {
+    memcpy(drow, &c.enc_matrix[size_t(sh) * k], k);
+    return;
+  }
+  const GfTables &gt = gft();
+  const int az = (sh - k - m) / c.local_m, lp = (sh - k - m) % c.local_m;
+  const std::vector<int32_t> idx = local_stripe(c.t, az);
+  const uint8_t *lr = &c.local_matrix[size_t(c.local_n + lp) * c.local_n];
+  memset(drow, 0, k);
+  for (int j = 0; j < c.local_n; j++) {
+    const uint8_t *er = &c.enc_matrix[size_t(idx[j]) * k];
+    for (int d = 0; d < k; d++) drow[d] ^= gt.mul[lr[j]][er[d]];
+  }
+}
+
+/* The decoding basis of one engine for one erasure set. */
+struct Basis {
+  int k = 0;
+  std::vector<int> valid;        /* the k inputs, engine indices */
+  std::vector<int> slot;         /* data column -> input slot, -1 = missing */
+  std::vector<uint8_t> is_input; /* per engine shard */
+  std::vector<uint8_t> dec;      /* k×k: data column d over the inputs */
+};
+
+/* first k present rows in index order (reedsolomon.go:1453-1466), inverted */
+static int basis_build(int k, int m, const uint8_t *matrix,
+                       const uint8_t *present, Basis *b) {
+  b->k = k;
+  b->slot.assign(k, -1);
+  b->is_input.assign(k + m, 0);
+  for (int i = 0; i < k + m && int(b->valid.size()) < k; i++)
+    if (present[i]) {
+      if (i < k) b->slot[i] = int(b->valid.size());
+      b->is_input[i] = 1;
+      b->valid.push_back(i);
+    }
+  if (int(b->valid.size()) < k) return GFRS_ERR_TOO_FEW_SHARDS;
+  std::vector<uint8_t> sub(size_t(k) * k);
+  b->dec.resize(size_t(k) * k);
+  for (int r = 0; r < k; r++)
+    memcpy(&sub[size_t(r) * k], &matrix[size_t(b->valid[r]) * k], k);
+  return gf_invert(sub.data(), k, b->dec.data()) ? GFRS_OK
+                                                  : GFRS_ERR_SINGULAR;
+}
+
+/* data-space row -> row over the k chosen inputs: a present data column is
+ * its own input slot, a missing one is substituted through dec
+ *   row[j] = drow[d]·1[slot(d)==j] (+) Σ_missing drow[d]·dec[d][j] */
+static void over_inputs(const Basis &b, const uint8_t *drow, uint8_t *row) {
+  const GfTables &gt = gft();
+  const int k = b.k;
+  memset(row, 0, k);
+  for (int d = 0; d < k; d++) {
+    const uint8_t coef = drow[d];
+    if (!coef) continue;
+    if (b.slot[d] >= 0)
+      row[b.slot[d]] ^= coef;
+    else
+      for (int j = 0; j < k; j++)
+        row[j] ^= gt.mul[coef][b.dec[size_t(d) * k + j]];
+  }
+}
+
+/* append shard `sh` as an output row, given its data-space row */
+static void add_row(Plan *p, const Basis &b, const uint8_t *drow, int sh) {
+  p->out.push_back(sh);
+  p->rows.resize(p->rows.size() + b.k);
+  over_inputs(b, drow, &p->rows[p->rows.size() - b.k]);
+}
+
+int plan_decode(const Engine &e, const uint8_t *present, Plan *p) {
+  Basis b;
+  int rc = basis_build(e.k, e.m, e.matrix, present, &b);
+  if (rc != GFRS_OK) return rc;
+  p->rowk = e.k;
+  for (int v : b.valid) p->in.push_back(e.idx[v]);
+  for (int i = 0; i < e.k; i++)
+    if (!present[i]) add_row(p, b, &e.matrix[size_t(i) * e.k], e.idx[i]);
+  return GFRS_OK;
+}
+
+int plan_parity(const Engine &e, const uint8_t *present, Plan *p) {
+  p->rowk = e.k;
+  for (int i = 0; i < e.k; i++) p->in.push_back(e.idx[i]);
+  for (int i = e.k; i < e.k + e.m; i++)
+    if (!present[i]) {
+      p->out.push_back(e.idx[i]);
+      p->rows.insert(p->rows.end(), &e.matrix[size_t(i) * e.k],
+                     &e.matrix[size_t(i) * e.k + e.k]);
+    }
+  return GFRS_OK;
+}
+
+int plan_encode_idx(const Code &c, int idx, Plan *p) {
+  if (idx < 0 || idx >= c.t.n) return GFRS_ERR_INVALID_SHARDS;
+  p->rowk = 1;
+  p->in.push_back(0);
+  for (int r = 0; r < c.t.m; r++) {
+    p->out.push_back(1 + r);
+    p->rows.push_back(c.enc_matrix[size_t(c.t.n + r) * c.t.n + idx]);
+  }
+  return GFRS_OK;
+}
+
+int plan_fused_lrc(const Code &c, Plan *p) {
+  const int k = c.t.n;
+  p->rowk = k;
+  for (int i = 0; i < k; i++) p->in.push_back(i);
+  for (int sh = k; sh < c.total; sh++) {
+    p->out.push_back(sh);
+    p->rows.resize(p->rows.size() + k);
+    dspace_row(c, sh, &p->rows[p->rows.size() - k]);
+  }
+  return GFRS_OK;
+}
+
+/* ---- reconstruct + verify / repair over the global engine ---- */
+
+/* bad list -> missing[] over all shards; the global basis for it */
+struct Erasure {
+  std::vector<uint8_t> missing; /* total */
+  Basis b;
+};
+
+static int erasure_build(const Code &c, const int32_t *bad, int nbad,
+                         bool dup_ok, Erasure *e) {
+  if (c.t.m <= 0) return GFRS_ERR_TOO_FEW_SHARDS;
+  e->missing.assign(c.total, 0);
+  for (int i = 0; i < nbad; i++) {
+    if (bad[i] < 0 || bad[i] >= c.total) return GFRS_ERR_INVALID_SHARDS;
+    if (e->missing[bad[i]] && !dup_ok) return GFRS_ERR_INVALID_SHARDS;
+    e->missing[bad[i]] = 1;
+  }
+  const int k = c.t.n, m = c.t.m;
+  std::vector<uint8_t> present(k + m);
+  for (int i = 0; i < k + m; i++) present[i] = !e->missing[i];
+  return basis_build(k, m, c.enc_matrix.data(), present.data(), &e->b);
+}
+
+static void add_shard(Plan *p, const Code &c, const Erasure &e, int sh) {
+  std::vector<uint8_t> drow(c.t.n);
+  dspace_row(c, sh, drow.data());
+  add_row(p, e.b, drow.data(), sh);
+}
+
+/* The check sequence of the single-pass paths: surviving global parities
+ * that are not inputs (an input parity's check is the identity), then
+ * surviving local parities (they restore detection when exactly k globals
+ * survive).  Stops once `out` holds max_rows; a check shard is appended to
+ * `in` when cmp_in is set. */
+static void add_checks(Plan *p, const Code &c, const Erasure &e,
+                       size_t max_rows, bool cmp_in) {
+  for (int sh = c.t.n; sh < c.total && p->out.size() < max_rows; sh++) {
+    if (e.missing[sh]) continue;
+    if (sh < c.t.n + c.t.m && e.b.is_input[sh]) continue;
+    add_shard(p, c, e, sh);
+    if (cmp_in) p->in.push_back(sh);
+  }
+}
+
+int plan_rs_reconstruct_verify(const Code &c, const int32_t *bad, int nbad,
+                               Plan *p) {
+  Erasure e;
+  int rc = erasure_build(c, bad, nbad, /*dup_ok=*/true, &e);
+  if (rc != GFRS_OK) return rc;
+  const int k = c.t.n, m = c.t.m;
+  p->rowk = k;
+  p->in.assign(e.b.valid.begin(), e.b.valid.end());
+  for (int i = 0; i < k; i++)
+    if (e.missing[i]) add_shard(p, c, e, i);
+  /* every parity row, inputs included: a missing one is written, a present
+   * one compared */
+  for (int sh = k; sh < k + m; sh++) {
+    if (!e.missing[sh]) p->cmp_mask |= 1u << p->out.size();
+    add_shard(p, c, e, sh);
+  }
+  return GFRS_OK;
+}
+
+int plan_lrc_reconstruct_verify(const Code &c, const int32_t *bad, int nbad,
+                                Plan *p) {
+  Erasure e;
+  int rc = erasure_build(c, bad, nbad, /*dup_ok=*/false, &e);
+  if (rc == GFRS_ERR_TOO_FEW_SHARDS) return GFRS_ERR_UNSUPPORTED;
+  if (rc != GFRS_OK) return rc;
+  p->rowk = c.t.n;
+  p->in.assign(e.b.valid.begin(), e.b.valid.end());
+  for (int i = 0; i < nbad; i++) add_shard(p, c, e, bad[i]);
+  add_checks(p, c, e, size_t(-1), /*cmp_in=*/false);
+  if (p->out.size() > 32) return GFRS_ERR_UNSUPPORTED; /* cmp_mask width */
+  for (size_t r = size_t(nbad); r < p->out.size(); r++)
+    p->cmp_mask |= 1u << r;
+  return GFRS_OK;
+}
+
+int repair_colpack(int total, const int32_t *bad, int nbad,
+                   uint32_t *colpack) {
+  if (nbad <= 0 || nbad > 4) return GFRS_ERR_UNSUPPORTED; /* 4-row budget */
+  *colpack = 0;
+  for (int i = 0; i < nbad; i++) {
+    if (bad[i] < 0 || bad[i] >= total) return GFRS_ERR_INVALID_SHARDS;
+    int rank = 0; /* row of bad[i] = its rank in ascending order */
+    for (int j = 0; j < nbad; j++) {
+      if (j != i && bad[j] == bad[i]) return GFRS_ERR_INVALID_SHARDS;
+      rank += bad[j] < bad[i];
+    }
+    *colpack |= uint32_t(i) << (4 * rank);
+  }
+  return GFRS_OK;
+}
+
+int plan_fused_repair(const Code &c, const int32_t *bad, int nbad, Plan *p) {
+  int rc = repair_colpack(c.total, bad, nbad, &p->colpack);
+  if (rc != GFRS_OK) return rc;
+  Erasure e;
+  if ((rc = erasure_build(c, bad, nbad, /*dup_ok=*/false, &e)) != GFRS_OK)
+    return rc;
+  p->rowk = c.t.n;
+  p->in.assign(e.b.valid.begin(), e.b.valid.end());
+  for (int sh = 0; sh < c.total; sh++) /* rebuild rows, ascending */
+    if (e.missing[sh]) add_shard(p, c, e, sh);
+  add_checks(p, c, e, 4, /*cmp_in=*/true);
+  for (size_t r = size_t(nbad); r < p->out.size(); r++)
+    p->cmp_mask |= 1u << r;
+  return GFRS_OK;
+}
+
+}  // namespace gfrs
+
+/* ---- GPU-free diagnostic export (include/gfrs.h) ---- */
+
+extern "C" int gfrs_compute_plan(const gfrs_tactic *t, int kind,
+                                 const int32_t *bad, int nbad, int cap,
+                                 int32_t *in, int *nin, int32_t *out,
+                                 int *nout, uint8_t *rows, int *rowk,
+                                 uint32_t *cmp_mask, uint32_t *colpack) {
+  using namespace gfrs;
+  if (!tactic_valid(t) || t->m == 0) return GFRS_ERR_INVALID_CODEMODE;
+  Code c;
+  if (!code_build(*t, &c)) return GFRS_ERR_SINGULAR;
+  Plan p;
+  int rc = GFRS_ERR_UNSUPPORTED;
+  if (kind == GFRS_PLAN_FUSED_LRC_ENCODE) rc = plan_fused_lrc(c, &p);
+  if (kind == GFRS_PLAN_RS_RECONSTRUCT_VERIFY)
+    rc = plan_rs_reconstruct_verify(c, bad, nbad, &p);
+  if (kind == GFRS_PLAN_LRC_RECONSTRUCT_VERIFY)
+    rc = plan_lrc_reconstruct_verify(c, bad, nbad, &p);
+  if (kind == GFRS_PLAN_FUSED_REPAIR) rc = plan_fused_repair(c, bad, nbad, &p);
+  if (rc != GFRS_OK) return rc;
+  if (int(p.in.size()) > cap || int(p.out.size()) > cap) return GFRS_ERR_NOMEM;
+  *nin = int(p.in.size());
+  *nout = int(p.out.size());
+  *rowk = p.rowk;
+  *cmp_mask = p.cmp_mask;
+  *colpack = p.colpack;
+  std::copy(p.in.begin(), p.in.end(), in);
+  std::copy(p.out.begin(), p.out.end(), out);
+  std::copy(p.rows.begin(), p.rows.end(), rows);
+  return GFRS_OK;
+}

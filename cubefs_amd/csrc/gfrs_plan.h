@@ -1,0 +1,115 @@
+/* cubefs_amd/csrc/gfrs_plan.h — GF(2^8) math and coding-plan construction.
+ *
+ * Plain host C++ with no device dependency: everything that decides which
+ * coefficients multiply which shards lives here, so it can be built and
+ * checked by a host compiler alone (tests/plan_selftest.cpp,
+ * tests/test_plan_cpu.py through gfrs_compute_plan).  gfrs_host.cpp uploads
+ * the plans and launches kernels; it holds no algebra.
+ */
+#ifndef GFRS_PLAN_H
+#define GFRS_PLAN_H
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/gfrs.h"
+
+namespace gfrs {
+
+/* ---- GF(2^8) field, poly 0x11D (generator 29; galois.go:25) ---- */
+struct GfTables {
+  uint8_t log_t[256];
+  uint8_t exp_t[510];
+  uint8_t mul[256][256];
+  /* nibble tables: lo[c][x] = mul[c][x], hi[c][x] = mul[c][x<<4]
+   * (galois.go:340,596) */
+  uint8_t lo[256][16];
+  uint8_t hi[256][16];
+  GfTables();
+  uint8_t gexp(uint8_t a, int n) const; /* galois.go:892 */
+  uint8_t div(uint8_t a, uint8_t b) const;
+};
+const GfTables &gft();
+
+/* Row-major byte matrix helpers (matrix.go). */
+bool gf_invert(const uint8_t *in, int n, uint8_t *out); /* false = singular */
+/* klauspost default encode matrix: vandermonde(total,k) × inv(top k×k)
+ * (reedsolomon.go:220-244).  out is total×k; its top k×k is the identity. */
+bool gf_build_matrix(int k, int total, uint8_t *out);
+
+/* ---- the code: what the plan builders need to know of a context ---- */
+struct Code {
+  gfrs_tactic t{};
+  int total = 0;   /* n+m+l */
+  int local_n = 0; /* (n+m)/az when l>0 */
+  int local_m = 0; /* l/az */
+  std::vector<uint8_t> enc_matrix;   /* (n+m)×n */
+  std::vector<uint8_t> local_matrix; /* (local_n+local_m)×local_n */
+};
+bool tactic_valid(const gfrs_tactic *t);   /* codemode.go:291-299 */
+bool code_build(const gfrs_tactic &t, Code *c); /* false = singular */
+/* local stripe global indices for one AZ (codemode.go:301-318) */
+std::vector<int32_t> local_stripe(const gfrs_tactic &t, int az_idx);
+
+/* One RS engine inside the code: its matrix ((k+m)×k) and the global shard
+ * slot of each of its k+m shards.  The global engine and the per-AZ local
+ * engines differ only in these. */
+struct Engine {
+  int k, m;
+  const uint8_t *matrix;
+  const int32_t *idx;
+};
+
+/* ---- a plan before upload ----
+ * For every output row r:  shard out[r] = XOR_c rows[r*rowk+c] * shard in[c].
+ * Conventions shared by every builder:
+ *   - decoding inputs are the first k present shards of the engine in index
+ *     order (reedsolomon.go:1453-1466);
+ *   - write rows come first, compare rows after them; cmp_mask has bit r
+ *     set when row r is compared against the stored shard, not written;
+ *   - `in` may carry more than rowk entries: the fused repair kernel finds
+ *     the stored shard of its r-th check row at in[rowk + r'];
+ *   - the fused repair kernel carries 4 rows in all (rebuild + check). */
+struct Plan {
+  std::vector<int32_t> in, out;
+  std::vector<uint8_t> rows; /* out.size() × rowk */
+  int rowk = 0;
+  uint32_t cmp_mask = 0;
+  uint32_t colpack = 0; /* fused repair: nibble r = caller's image column
+                           of the r-th rebuild row */
+};
+
+/* Every builder returns GFRS_OK or an error code and leaves *p complete.
+ * `present` covers the engine's k+m shards. */
+
+/* missing data shards of one engine from its first k present shards */
+int plan_decode(const Engine &e, const uint8_t *present, Plan *p);
+/* missing parity shards of one engine from its k data shards; an empty
+ * `out` means there is nothing to do */
+int plan_parity(const Engine &e, const uint8_t *present, Plan *p);
+/* EncodeIdx accumulate: input slot 0, the m global parities at 1..m */
+int plan_encode_idx(const Code &c, int idx, Plan *p);
+/* all m global then all l local parities (az-major) as rows over the n
+ * data shards */
+int plan_fused_lrc(const Code &c, Plan *p);
+/* plain RS reconstruct+verify: missing data ascending, then ALL m parity
+ * rows; present parities are compared.  Duplicates in bad are tolerated. */
+int plan_rs_reconstruct_verify(const Code &c, const int32_t *bad, int nbad,
+                               Plan *p);
+/* LRC reconstruct+verify: bad shards in caller order, then the check rows:
+ * surviving global parities that are not inputs, surviving local parities.
+ * GFRS_ERR_UNSUPPORTED when the bad set is not globally decodable or needs
+ * more than 32 rows (the caller falls back to two passes). */
+int plan_lrc_reconstruct_verify(const Code &c, const int32_t *bad, int nbad,
+                                Plan *p);
+/* fused repair: bad shards ascending, then the same check rows while the
+ * 4-row budget lasts */
+int plan_fused_repair(const Code &c, const int32_t *bad, int nbad, Plan *p);
+/* the colpack of plan_fused_repair alone (it depends on the caller's order,
+ * which a cached plan does not know); also its bad-list validation */
+int repair_colpack(int total, const int32_t *bad, int nbad, uint32_t *colpack);
+
+}  // namespace gfrs
+
+#endif

@@ -146,6 +146,12 @@ def lib():
                                         ctypes.c_int, i32p, ctypes.c_int, vp,
                                         ctypes.c_size_t, i64, u64p, u64p, u64p]
         L.gfrs_encode_matrix.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8)]
+        u8p, ip = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        L.gfrs_compute_plan.argtypes = [ctypes.POINTER(Tactic), ctypes.c_int,
+                                        i32p, ctypes.c_int, ctypes.c_int,
+                                        i32p, ip, i32p, ip, u8p, ip, u32p,
+                                        u32p]
         _lib = L
     return _lib
 

@@ -311,6 +311,24 @@ int gfrs_encode_matrix(gfrs_ctx *ctx, uint8_t *out);
 /* GPU-free: compute the klauspost default encode matrix (total×k) so CPU
  * tests can pin the host math without a device. */
 int gfrs_compute_encode_matrix(int k, int total, uint8_t *out);
+/* GPU-free: build the coding plan the engine would upload for one bad list,
+ * with the same builder functions, so CPU tests can check every erasure
+ * pattern without a device.  For each r < *nout,
+ *   shard out[r] = XOR_c rows[r * *rowk + c] * shard in[c];
+ * bit r of *cmp_mask marks a row the kernel compares instead of writing.
+ * `in` and `out` hold `cap` entries, `rows` cap * n bytes (GFRS_ERR_NOMEM
+ * when the plan is larger).  `bad` is ignored for the encode kind.
+ * Returns the builder's error code. */
+enum {
+  GFRS_PLAN_FUSED_LRC_ENCODE = 0,       /* gfrs_encode_frame_batch, LRC */
+  GFRS_PLAN_RS_RECONSTRUCT_VERIFY = 1,  /* gfrs_reconstruct_verify_batch */
+  GFRS_PLAN_LRC_RECONSTRUCT_VERIFY = 2, /* the same, LRC single pass */
+  GFRS_PLAN_FUSED_REPAIR = 3,           /* gfrs_repair_batch, fused kernel */
+};
+int gfrs_compute_plan(const gfrs_tactic *t, int kind, const int32_t *bad,
+                      int nbad, int cap, int32_t *in, int *nin, int32_t *out,
+                      int *nout, uint8_t *rows, int *rowk, uint32_t *cmp_mask,
+                      uint32_t *colpack);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);
