@@ -229,6 +229,8 @@ struct gfrs_ctx_impl {
   DevBuf fail_buf;  /* verify flags / crc bad blocks */
   DevBuf stage_dev; /* host-mode staging */
   PinBuf stage_pin;
+  DevBuf queue_buf; /* repair queue: pattern descriptors, work items, tile
+                       prefix sums of one call */
 
   /* finalize-pipeline resources (repair path): shard_finalize of chunk i
    * runs on aux_stream behind an event while chunk i+1's repair kernel
@@ -331,7 +333,7 @@ static bool upload_fixed_plans(gfrs_ctx_impl *c) {
     if (ok) /* one local-stripe set, identity indices */
       ok = encode_plan(cd.local_n, cd.local_m, cd.local_matrix, ident,
                        &c->local_plan);
-    if (ok && t.m + t.l <= 4 && cd.total <= 16) {
+    if (ok && lrc_single_pass(cd)) {
       Plan pl;
       plan_fused_lrc(cd, &pl);
       ok = c->fused_lrc.upload(pl, c->stream) == GFRS_OK;
@@ -1298,6 +1300,107 @@ int gfrs_reconstruct_verify_batch(gfrs_ctx *ctx, void *base,
   if (rc != GFRS_OK) return rc;
   return gfrs_verify_batch(ctx, base, shard_len, stripe_stride, nstripes,
                            fail_bitmap);
+}
+
+/* The repair queue: per-job erasure pattern and shard length, a bounded
+ * number of launches, one sync.  gfrs_plan.cpp validates the patterns,
+ * builds their plans (cached here like the batch call's, same namespaces)
+ * and decides which job runs in which launch; this function uploads the
+ * schedule and issues it.  Jobs of slow patterns follow as the two passes
+ * gfrs_reconstruct_verify_batch falls back to, without its locks and sync. */
+int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
+                                  const gfrs_qjob *jobs, int njobs,
+                                  const int32_t *bad_idx,
+                                  const int32_t *bad_off, int npat,
+                                  uint64_t *fail_bitmap) {
+  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+  const Code &cd = c->code;
+  const bool lrc = cd.t.l != 0;
+  if (njobs <= 0 || npat <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
+  int rc = queue_offsets_check(bad_off, npat);
+  if (rc != GFRS_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+
+  /* every pattern, used or not: validate, then find or build its plan */
+  std::vector<QueuePattern> pats(npat);
+  std::vector<DevPlan *> plans(npat, nullptr);
+  for (int p = 0; p < npat; p++) {
+    const int32_t *bad = bad_idx + bad_off[p];
+    const int nbad = bad_off[p + 1] - bad_off[p];
+    if ((rc = queue_pattern_check(cd, bad, nbad, &pats[p].slow)) != GFRS_OK)
+      return rc;
+    if (pats[p].slow) continue;
+    PlanKey key;
+    rc = bad_list_key(lrc ? 60 : 63, bad, nbad, cd.total, /*dup_ok=*/!lrc,
+                      &key);
+    if (rc != GFRS_OK) return rc;
+    auto build = [&](Plan *pl) {
+      QueuePattern q;
+      int brc = queue_pattern(cd, bad, nbad, pl, &q);
+      /* the batch call's fallback signal; cached_plan caches no failure */
+      return brc == GFRS_OK && q.slow ? int(GFRS_ERR_UNSUPPORTED) : brc;
+    };
+    rc = cached_plan(c, c->dec_cache, key, c->stream, std::ref(build),
+                     &plans[p]);
+    if (rc == GFRS_ERR_UNSUPPORTED) {
+      pats[p].slow = true;
+      continue;
+    }
+    if (rc != GFRS_OK) return rc;
+    pats[p].nout = plans[p]->nout;
+  }
+  QueueSchedule sched;
+  if ((rc = queue_schedule(jobs, njobs, pats.data(), npat, &sched)) != GFRS_OK)
+    return rc;
+
+  /* one upload: [npat descriptors | work items | tile prefix sums] */
+  const size_t o_items = size_t(npat) * sizeof(QueuePat);
+  const size_t o_prefix = o_items + sched.items.size() * sizeof(gfrs_qitem);
+  const size_t nbytes = o_prefix + sched.tile_prefix.size() * 8;
+  std::vector<uint8_t> blob(nbytes);
+  for (int p = 0; p < npat; p++) {
+    QueuePat d{};
+    if (plans[p])
+      d = QueuePat{plans[p]->in(), plans[p]->out(), plans[p]->tab(),
+                   plans[p]->cmp_mask, plans[p]->nout};
+    memcpy(&blob[size_t(p) * sizeof(QueuePat)], &d, sizeof(d));
+  }
+  if (!sched.items.empty()) {
+    memcpy(&blob[o_items], sched.items.data(), o_prefix - o_items);
+    memcpy(&blob[o_prefix], sched.tile_prefix.data(), nbytes - o_prefix);
+  }
+  if ((rc = c->queue_buf.ensure(nbytes)) != GFRS_OK) return rc;
+  if ((rc = fail_begin(&c->fail_buf, njobs, c->stream)) != GFRS_OK) return rc;
+  /* blob stays alive until fail_finish has synchronized the stream */
+  HIP_TRY(hipMemcpyAsync(c->queue_buf.p, blob.data(), nbytes,
+                         hipMemcpyHostToDevice, c->stream));
+  const uint8_t *dq = (const uint8_t *)c->queue_buf.p;
+  uint32_t *fail = (uint32_t *)c->fail_buf.p;
+  for (const QueueBucket &b : sched.buckets)
+    launch_rs_apply_queue(
+        (uint64_t)base, (const gfrs_qitem *)(dq + o_items) + b.first,
+        (const uint64_t *)(dq + o_prefix) + b.prefix, uint32_t(b.count),
+        sched.tile_prefix[b.prefix + b.count], (const QueuePat *)dq, cd.t.n,
+        b.gm, fail, c->stream);
+  for (int32_t j : sched.slow_jobs) {
+    const gfrs_qjob &jb = jobs[j];
+    const int32_t *bad = bad_idx + bad_off[jb.pattern];
+    const int nbad = bad_off[jb.pattern + 1] - bad_off[jb.pattern];
+    std::vector<uint8_t> present(cd.total, 1);
+    for (int i = 0; i < nbad; i++) present[bad[i]] = 0;
+    const Shards sh = strided((const uint8_t *)base + jb.off, 0);
+    rc = reconstruct_all(c, view_of(c), present, jb.shard_len, 1,
+                         /*data_only=*/0, sh);
+    if (rc != GFRS_OK) break;
+    run_encode_plans(OP_VERIFY, c, sh, jb.shard_len, 1, c->stream, fail + j);
+  }
+  hipError_t e = hipGetLastError();
+  if (rc != GFRS_OK || e != hipSuccess) {
+    hipStreamSynchronize(c->stream); /* blob is still being read */
+    return rc != GFRS_OK ? rc : hip_fail("reconstruct_verify_queue launch", e);
+  }
+  return fail_finish(&c->fail_buf, njobs, c->stream, fail_bitmap);
 }
 
 int gfrs_update_idx(gfrs_ctx *ctx, const void *old_shard,

@@ -101,6 +101,27 @@ void launch_rs_apply_mixed_strided(uint64_t base, uint64_t stripe_stride,
                                    size_t shard_len, int nstripes,
                                    uint32_t *fail, hipStream_t s);
 
+/* Repair queue: one bucket of the schedule (gfrs_plan.h), i.e. every
+ * (job, step) pair with the same step index and the same row count gm.
+ * Each work item is a mixed write/compare apply of gm rows of its own
+ * pattern's plan, starting at its row_off, over its own job:
+ *   shard i of the job at base + item.off + i * item.shard_len.
+ * pats[item.pattern] describes that plan (device pointers into the cached
+ * DevPlans); tile_prefix holds the nitems+1 exclusive prefix sums of
+ * ceil(shard_len / 4096), total_tiles its last entry.  Mismatches of compare
+ * rows are ORed into fail[item.job].  All arrays are device memory. */
+struct QueuePat {
+  const int32_t *in_idx;  /* k inputs */
+  const int32_t *out_idx; /* nout rows */
+  const uint8_t *tabs;    /* [nout*k][32] */
+  uint32_t cmp_mask;
+  int32_t nout;
+};
+void launch_rs_apply_queue(uint64_t base, const gfrs_qitem *items,
+                           const uint64_t *tile_prefix, uint32_t nitems,
+                           uint64_t total_tiles, const QueuePat *pats, int k,
+                           int gm, uint32_t *fail, hipStream_t s);
+
 /* EncodeIdx-style accumulate apply (reedsolomon.go:631-668):
  * out[r] ^= coeff[r]*in for one input shard. */
 void launch_rs_apply_xor(const uint64_t *ptrs, int nptr,

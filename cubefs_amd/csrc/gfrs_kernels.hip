@@ -433,6 +433,187 @@ void launch_rs_apply_mixed_strided(uint64_t base, uint64_t stripe_stride,
   }
 }
 
+/* ---- repair queue: per-job pattern and shard length ---- */
+
+/* One bucket of a queue schedule (gfrs_plan.h): GM rows of each work item's
+ * own plan over its own job.  Same math as rs_apply_k; what differs is where
+ * a tile comes from:
+ *  - the grid is capped and block b walks the CONTIGUOUS tile range
+ *    [b*per_blk, (b+1)*per_blk) of the bucket, so with the items ordered by
+ *    pattern a block rarely changes tables;
+ *  - tile -> work item: one binary search over the tile prefix sums at the
+ *    block's first tile, then a forward walk (every item has >= 1 tile).
+ *    Everything involved depends on blockIdx and kernel arguments only, so
+ *    the search, the item and the pattern descriptor are scalar loads;
+ *  - the k*GM*32 bytes of tables are restaged into LDS only when the pattern
+ *    or the row offset of the next tile differs from what is loaded, between
+ *    two barriers.  The test is block-uniform and no lane leaves the loop
+ *    body early, so every lane reaches both barriers;
+ *  - a job shorter than a tile still takes a whole tile (no packing of
+ *    small jobs; lanes past shard_len idle);
+ *  - a block works on one job at a time, so the ballot form of the fail
+ *    report is exact. */
+template <int GM>
+__global__ __launch_bounds__(RS_BLOCK) void rs_apply_queue_k(
+    uint64_t base, const gfrs_qitem *__restrict__ items,
+    const uint64_t *__restrict__ tile_prefix, uint32_t nitems,
+    uint64_t total_tiles, const QueuePat *__restrict__ pats, int k,
+    uint32_t *fail) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint4 *ltab = reinterpret_cast<uint4 *>(smem); /* [k*GM*2] */
+
+  const uint64_t per_blk = (total_tiles + gridDim.x - 1) / gridDim.x;
+  const uint64_t t_lo = uint64_t(blockIdx.x) * per_blk;
+  const uint64_t t_hi =
+      t_lo + per_blk < total_tiles ? t_lo + per_blk : total_tiles;
+  if (t_lo >= t_hi) return; /* whole block, before any barrier */
+
+  /* largest it with tile_prefix[it] <= t_lo (tile_prefix[0] == 0) */
+  uint32_t it = 0;
+  for (uint32_t hi = nitems; hi - it > 1;) {
+    const uint32_t mid = it + (hi - it) / 2;
+    if (tile_prefix[mid] <= t_lo)
+      it = mid;
+    else
+      hi = mid;
+  }
+
+  /* the index lists arrive as pointers read from the descriptor table:
+   * the constant address space keeps their (block-uniform) reads scalar,
+   * as they are in rs_apply_k where the lists are kernel arguments */
+  typedef const __attribute__((address_space(4))) int32_t *IdxList;
+  int cur_pat = -1, cur_row = -1;
+  IdxList in_idx = nullptr, out_idx = nullptr;
+  uint32_t cmp_mask = 0;
+
+  for (uint64_t tile = t_lo; tile < t_hi; tile++) {
+    while (tile_prefix[it + 1] <= tile) it++; /* it + 1 <= nitems */
+    const gfrs_qitem item = items[it];
+    const size_t shard_len = item.shard_len;
+    const uint64_t job_base = base + item.off;
+    if (item.pattern != cur_pat || item.row_off != cur_row) {
+      const QueuePat pat = pats[item.pattern];
+      __syncthreads(); /* all lanes are done with the old tables */
+      const uint4 *src = reinterpret_cast<const uint4 *>(as_global(
+          uint64_t(pat.tabs) + uint64_t(item.row_off) * k * 32));
+      for (int i = threadIdx.x; i < k * GM * 2; i += RS_BLOCK)
+        ltab[i] = src[i];
+      __syncthreads();
+      cur_pat = item.pattern;
+      cur_row = item.row_off;
+      in_idx = (IdxList)(uint64_t)pat.in_idx;
+      out_idx = (IdxList)(uint64_t)(pat.out_idx + item.row_off);
+      cmp_mask = (pat.cmp_mask >> item.row_off) & ((1u << GM) - 1);
+    }
+    const size_t off = size_t(tile - tile_prefix[it]) * size_t(RS_TILE) +
+                       size_t(threadIdx.x) * 16;
+    bool mismatch = false;
+
+    if (off + 16 <= shard_len) {
+      uint4 acc[GM];
+#pragma unroll
+      for (int r = 0; r < GM; r++) acc[r] = uint4{0, 0, 0, 0};
+      constexpr int KB = 8; /* input loads in flight, as in rs_apply_k */
+      for (int c0 = 0; c0 < k; c0 += KB) {
+        uint4 v[KB];
+#pragma unroll
+        for (int j = 0; j < KB; j++) {
+          if (c0 + j < k) {
+            const uint8_t *in =
+                as_global(job_base + uint64_t(in_idx[c0 + j]) * shard_len);
+            v[j] = *reinterpret_cast<const uint4 *>(in + off);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < KB; j++) {
+          if (c0 + j < k) {
+            LinTab lt[GM];
+#pragma unroll
+            for (int r = 0; r < GM; r++)
+              lt[r] = lintab_load(smem, r * k + c0 + j);
+#pragma unroll
+            for (int d = 0; d < 4; d++) {
+              const uint32_t w = (&v[j].x)[d];
+              const uint32_t s012 = w & 0x07070707u;
+              const uint32_t s345 = (w >> 3) & 0x07070707u;
+              const uint32_t s67 = (w >> 6) & 0x03030303u;
+#pragma unroll
+              for (int r = 0; r < GM; r++)
+                (&acc[r].x)[d] ^= gfmul4_lin(s012, s345, s67, lt[r]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < GM; r++) {
+        uint8_t *out = const_cast<uint8_t *>(
+            as_global(job_base + uint64_t(out_idx[r]) * shard_len));
+        if ((cmp_mask >> r) & 1) {
+          const uint4 e = *reinterpret_cast<const uint4 *>(out + off);
+          mismatch |= (e.x != acc[r].x) | (e.y != acc[r].y) |
+                      (e.z != acc[r].z) | (e.w != acc[r].w);
+        } else {
+          store16<false>(out + off, acc[r]);
+        }
+      }
+    } else if (off < shard_len) {
+      /* ragged tail: per-byte path using the byte view of the LDS tables */
+      const size_t nb = shard_len - off;
+      for (int og = 0; og < GM; og++) {
+        const uint8_t *trow = smem + size_t(og * k) * 32;
+        uint8_t *out = const_cast<uint8_t *>(
+            as_global(job_base + uint64_t(out_idx[og]) * shard_len));
+        for (size_t i = 0; i < nb; i++) {
+          uint8_t v = 0;
+          for (int c = 0; c < k; c++) {
+            const uint8_t b = as_global(
+                job_base + uint64_t(in_idx[c]) * shard_len)[off + i];
+            v ^= gfmul1_lin(trow + size_t(c) * 32, b);
+          }
+          if ((cmp_mask >> og) & 1)
+            mismatch |= (out[off + i] != v);
+          else
+            out[off + i] = v;
+        }
+      }
+    }
+    if (cmp_mask && __ballot(mismatch) != 0) {
+      if ((threadIdx.x & 63) == 0) atomicOr(&fail[item.job], 1u);
+    }
+  }
+}
+
+template <int GM>
+static void rs_queue_launch_one(uint64_t base, const gfrs_qitem *items,
+                                const uint64_t *tile_prefix, uint32_t nitems,
+                                uint64_t total_tiles, const QueuePat *pats,
+                                int k, uint32_t *fail, hipStream_t s) {
+  /* the cap of rs_grid, so GFRS_RS_GRID forces the multi-tile walk and the
+   * restage path at tiny shapes */
+  const uint64_t cap = uint64_t(env_grid("GFRS_RS_GRID", 256 * 64));
+  const int grid = int(total_tiles < cap ? total_tiles : cap);
+  hipLaunchKernelGGL((rs_apply_queue_k<GM>), dim3(grid), dim3(RS_BLOCK),
+                     k * GM * 32, s, base, items, tile_prefix, nitems,
+                     total_tiles, pats, k, fail);
+}
+
+void launch_rs_apply_queue(uint64_t base, const gfrs_qitem *items,
+                           const uint64_t *tile_prefix, uint32_t nitems,
+                           uint64_t total_tiles, const QueuePat *pats, int k,
+                           int gm, uint32_t *fail, hipStream_t s) {
+  if (nitems == 0 || total_tiles == 0) return;
+  switch (gm) {
+    case 1: rs_queue_launch_one<1>(base, items, tile_prefix, nitems,
+                                   total_tiles, pats, k, fail, s); break;
+    case 2: rs_queue_launch_one<2>(base, items, tile_prefix, nitems,
+                                   total_tiles, pats, k, fail, s); break;
+    case 3: rs_queue_launch_one<3>(base, items, tile_prefix, nitems,
+                                   total_tiles, pats, k, fail, s); break;
+    default: rs_queue_launch_one<4>(base, items, tile_prefix, nitems,
+                                    total_tiles, pats, k, fail, s);
+  }
+}
+
 /* EncodeIdx-style accumulate apply: out[r] ^= coeff[r]*in (one input). */
 void launch_rs_apply_xor(const uint64_t *ptrs, int nptr,
                          const int32_t *in_idx, int k,

@@ -294,9 +294,184 @@ int plan_fused_repair(const Code &c, const int32_t *bad, int nbad, Plan *p) {
   return GFRS_OK;
 }
 
+bool lrc_single_pass(const Code &c) {
+  return c.t.l > 0 && c.t.m + c.t.l <= 4 && c.total <= 16;
+}
+
+/* ---- the repair queue ---- */
+
+int queue_offsets_check(const int32_t *bad_off, int npat) {
+  if (npat <= 0 || !bad_off || bad_off[0] != 0) return GFRS_ERR_INVALID_SHARDS;
+  for (int p = 0; p < npat; p++)
+    if (bad_off[p + 1] < bad_off[p]) return GFRS_ERR_INVALID_SHARDS;
+  return GFRS_OK;
+}
+
+int queue_pattern_check(const Code &c, const int32_t *bad, int nbad,
+                        bool *slow) {
+  *slow = false;
+  if (nbad < 0) return GFRS_ERR_INVALID_SHARDS;
+  const bool lrc = c.t.l > 0;
+  std::vector<uint8_t> seen(c.total, 0);
+  int nglobal = 0;
+  for (int i = 0; i < nbad; i++) {
+    if (bad[i] < 0 || bad[i] >= c.total) return GFRS_ERR_INVALID_SHARDS;
+    if (seen[bad[i]]) {
+      /* plain RS tolerates a repeated index, the LRC plans do not */
+      if (lrc) return GFRS_ERR_INVALID_SHARDS;
+      continue;
+    }
+    seen[bad[i]] = 1;
+    nglobal += bad[i] < c.t.n + c.t.m;
+  }
+  /* the full-width Reconstruct decodes the global stripe first
+   * (lrcencoder.go:155-186): more than m global losses fail whatever the
+   * local parities could have restored */
+  if (nglobal > c.t.m) return GFRS_ERR_TOO_FEW_SHARDS;
+  if (lrc && !lrc_single_pass(c)) *slow = true;
+  return GFRS_OK;
+}
+
+int queue_pattern(const Code &c, const int32_t *bad, int nbad, Plan *p,
+                  QueuePattern *q) {
+  *q = QueuePattern();
+  int rc = queue_pattern_check(c, bad, nbad, &q->slow);
+  if (rc != GFRS_OK || q->slow) return rc;
+  if (c.t.l > 0) {
+    rc = plan_lrc_reconstruct_verify(c, bad, nbad, p);
+    if (rc == GFRS_ERR_UNSUPPORTED) { /* more rows than cmp_mask has bits */
+      *p = Plan();
+      q->slow = true;
+      return GFRS_OK;
+    }
+  } else {
+    rc = plan_rs_reconstruct_verify(c, bad, nbad, p);
+  }
+  if (rc == GFRS_OK) q->nout = int(p->out.size());
+  return rc;
+}
+
+int queue_schedule(const gfrs_qjob *jobs, int njobs, const QueuePattern *pats,
+                   int npat, QueueSchedule *out) {
+  *out = QueueSchedule();
+  if (njobs <= 0 || npat <= 0 || !jobs || !pats) return GFRS_ERR_INVALID_SHARDS;
+  int max_steps = 0;
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_qjob &jb = jobs[j];
+    if (jb.pattern < 0 || jb.pattern >= npat || jb.reserved != 0)
+      return GFRS_ERR_INVALID_SHARDS;
+    if (jb.shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
+    const int steps = (pats[jb.pattern].nout + QUEUE_ROWS - 1) / QUEUE_ROWS;
+    max_steps = std::max(max_steps, steps);
+  }
+  /* jobs by pattern, caller order inside one pattern (counting sort) */
+  std::vector<size_t> pstart(size_t(npat) + 1, 0);
+  for (int j = 0; j < njobs; j++) pstart[size_t(jobs[j].pattern) + 1]++;
+  for (int p = 0; p < npat; p++) pstart[p + 1] += pstart[p];
+  std::vector<int32_t> order(njobs);
+  for (int j = 0; j < njobs; j++) order[pstart[jobs[j].pattern]++] = j;
+
+  /* bucket slot of step g with gm rows: ascending g, then gm */
+  auto slot = [](int g, int gm) { return size_t(g) * QUEUE_ROWS + (gm - 1); };
+  auto rows_of = [&](int nout, int g) {
+    return std::min(QUEUE_ROWS, nout - QUEUE_ROWS * g);
+  };
+  std::vector<size_t> count(size_t(max_steps) * QUEUE_ROWS, 0);
+  for (int j = 0; j < njobs; j++) {
+    const QueuePattern &qp = pats[jobs[j].pattern];
+    if (qp.slow) {
+      out->slow_jobs.push_back(j);
+      continue;
+    }
+    for (int g = 0; QUEUE_ROWS * g < qp.nout; g++)
+      count[slot(g, rows_of(qp.nout, g))]++;
+  }
+  std::vector<size_t> bucket_of(count.size(), size_t(-1)), fill(count.size());
+  size_t nitems = 0;
+  for (size_t s = 0; s < count.size(); s++) {
+    if (!count[s]) continue;
+    QueueBucket b;
+    b.g = int(s / QUEUE_ROWS);
+    b.gm = int(s % QUEUE_ROWS) + 1;
+    b.first = nitems;
+    b.count = count[s];
+    b.prefix = nitems + out->buckets.size();
+    bucket_of[s] = out->buckets.size();
+    fill[s] = nitems;
+    nitems += count[s];
+    out->buckets.push_back(b);
+  }
+  out->items.resize(nitems);
+  out->tile_prefix.assign(nitems + out->buckets.size(), 0);
+  for (int32_t j : order) {
+    const gfrs_qjob &jb = jobs[j];
+    const QueuePattern &qp = pats[jb.pattern];
+    if (qp.slow) continue;
+    for (int g = 0; QUEUE_ROWS * g < qp.nout; g++) {
+      const size_t s = slot(g, rows_of(qp.nout, g));
+      const QueueBucket &b = out->buckets[bucket_of[s]];
+      const size_t at = fill[s]++;
+      gfrs_qitem &it = out->items[at];
+      it.off = jb.off;
+      it.shard_len = jb.shard_len;
+      it.job = j;
+      it.pattern = jb.pattern;
+      it.row_off = QUEUE_ROWS * g;
+      it.reserved = 0;
+      const size_t pi = b.prefix + (at - b.first);
+      out->tile_prefix[pi + 1] =
+          out->tile_prefix[pi] + (jb.shard_len - 1) / QUEUE_TILE + 1;
+    }
+  }
+  return GFRS_OK;
+}
+
 }  // namespace gfrs
 
 /* ---- GPU-free diagnostic export (include/gfrs.h) ---- */
+
+extern "C" int gfrs_compute_queue_schedule(
+    const gfrs_tactic *t, const gfrs_qjob *jobs, int njobs,
+    const int32_t *bad_idx, const int32_t *bad_off, int npat, int item_cap,
+    int bucket_cap, gfrs_qitem *items, uint64_t *tile_prefix, int *nitems,
+    gfrs_qbucket *buckets, int *nbuckets, int32_t *pat_nout,
+    uint8_t *pat_slow, int32_t *slow_jobs, int *nslow) {
+  using namespace gfrs;
+  if (!tactic_valid(t) || t->m == 0) return GFRS_ERR_INVALID_CODEMODE;
+  if (njobs <= 0 || npat <= 0) return GFRS_ERR_INVALID_SHARDS;
+  int rc = queue_offsets_check(bad_off, npat);
+  if (rc != GFRS_OK) return rc;
+  Code c;
+  if (!code_build(*t, &c)) return GFRS_ERR_SINGULAR;
+  std::vector<QueuePattern> pats(npat);
+  for (int p = 0; p < npat; p++) {
+    Plan pl;
+    rc = queue_pattern(c, bad_idx + bad_off[p], bad_off[p + 1] - bad_off[p],
+                       &pl, &pats[p]);
+    if (rc != GFRS_OK) return rc;
+  }
+  QueueSchedule s;
+  if ((rc = queue_schedule(jobs, njobs, pats.data(), npat, &s)) != GFRS_OK)
+    return rc;
+  if (s.items.size() > size_t(item_cap < 0 ? 0 : item_cap) ||
+      s.buckets.size() > size_t(bucket_cap < 0 ? 0 : bucket_cap))
+    return GFRS_ERR_NOMEM;
+  *nitems = int(s.items.size());
+  *nbuckets = int(s.buckets.size());
+  *nslow = int(s.slow_jobs.size());
+  std::copy(s.items.begin(), s.items.end(), items);
+  std::copy(s.tile_prefix.begin(), s.tile_prefix.end(), tile_prefix);
+  for (size_t b = 0; b < s.buckets.size(); b++)
+    buckets[b] = gfrs_qbucket{s.buckets[b].g, s.buckets[b].gm,
+                              int32_t(s.buckets[b].first),
+                              int32_t(s.buckets[b].count)};
+  for (int p = 0; p < npat; p++) {
+    pat_nout[p] = pats[p].nout;
+    pat_slow[p] = pats[p].slow;
+  }
+  std::copy(s.slow_jobs.begin(), s.slow_jobs.end(), slow_jobs);
+  return GFRS_OK;
+}
 
 extern "C" int gfrs_compute_plan(const gfrs_tactic *t, int kind,
                                  const int32_t *bad, int nbad, int cap,

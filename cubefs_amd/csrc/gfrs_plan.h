@@ -110,6 +110,60 @@ int plan_fused_repair(const Code &c, const int32_t *bad, int nbad, Plan *p);
  * which a cached plan does not know); also its bad-list validation */
 int repair_colpack(int total, const int32_t *bad, int nbad, uint32_t *colpack);
 
+/* whether the LRC entry points take the composed single-pass plans for this
+ * code (the row and width budget of the fused kernels) */
+bool lrc_single_pass(const Code &c);
+
+/* ---- the repair queue (gfrs_reconstruct_verify_queue) ----
+ * Besides "which coefficients multiply which shards" the plan module decides
+ * "which job runs in which launch".  A job whose pattern has nout rows needs
+ * ceil(nout / QUEUE_ROWS) steps; step g carries gm = 1..QUEUE_ROWS rows at
+ * row offset QUEUE_ROWS * g.  All (job, step) pairs with the same (g, gm)
+ * form one bucket = one launch of the gm-row queue kernel, so a queue costs
+ * at most QUEUE_ROWS * ceil(max_nout / QUEUE_ROWS) launches whatever njobs
+ * and npat are.  Buckets are ordered by ascending g, then gm. */
+constexpr int QUEUE_ROWS = 4;        /* rows per launch (the kernels' MT) */
+constexpr uint64_t QUEUE_TILE = 4096; /* bytes of one shard per block step
+                                         (the kernels' RS_TILE) */
+
+struct QueuePattern {
+  int nout = 0;      /* rows of the pattern's plan (0 when slow) */
+  bool slow = false; /* no single-pass plan: the host runs its jobs one at a
+                        time through reconstruct + verify */
+};
+
+/* Validate one erasure pattern the way gfrs_reconstruct_verify_batch would
+ * and build its plan.  GFRS_OK with q->slow set leaves *p empty. */
+int queue_pattern(const Code &c, const int32_t *bad, int nbad, Plan *p,
+                  QueuePattern *q);
+/* The validation alone (what a plan-cache hit still has to decide). */
+int queue_pattern_check(const Code &c, const int32_t *bad, int nbad,
+                        bool *slow);
+
+struct QueueBucket {
+  int g = 0, gm = 0;
+  size_t first = 0, count = 0; /* its work items: items[first, first+count) */
+  size_t prefix = 0; /* its count+1 tile prefix sums start at
+                        tile_prefix[prefix] (= first + bucket index) */
+};
+
+struct QueueSchedule {
+  std::vector<gfrs_qitem> items;     /* every bucket's items, back to back;
+                                        inside a bucket ordered by pattern,
+                                        then by caller index */
+  std::vector<uint64_t> tile_prefix; /* exclusive prefix sums of
+                                        ceil(shard_len / QUEUE_TILE) */
+  std::vector<QueueBucket> buckets;
+  std::vector<int32_t> slow_jobs;    /* caller order */
+};
+
+/* GFRS_ERR_INVALID_SHARDS: njobs <= 0, npat <= 0, pattern out of range,
+ * reserved != 0; GFRS_ERR_SHARD_NO_DATA: shard_len == 0. */
+int queue_schedule(const gfrs_qjob *jobs, int njobs, const QueuePattern *pats,
+                   int npat, QueueSchedule *out);
+/* bad_off: npat+1 non-decreasing entries starting at 0 */
+int queue_offsets_check(const int32_t *bad_off, int npat);
+
 }  // namespace gfrs
 
 #endif

@@ -15,7 +15,7 @@ import io
 
 import numpy as np
 
-from . import codemode
+from . import codemode, runtime
 from .runtime import GfrsError, MEM_DEVICE, MEM_HOST, Tactic, check, lib
 
 
@@ -270,6 +270,35 @@ class Encoder:
         import numpy as np
         bmn = np.ctypeslib.as_array(bm)
         bits = np.unpackbits(bmn.view(np.uint8), bitorder="little")[:ns]
+        return bits.astype(bool).tolist()
+
+    def reconstruct_verify_queue(self, batch, jobs, patterns):
+        """Repair queue (worker_slice_recover.go:804-888, the loop over
+        bids): every job has its own place, shard length and erasure
+        pattern, and the whole queue is a bounded number of launches with
+        one sync.  batch: flat uint8 device tensor holding every job;
+        jobs: [(off, shard_len, pattern)], shard i of a job at byte
+        off + i*shard_len of batch; patterns: [[bad shard indices]], an
+        empty list meaning verify only.  Returns the per-job verify-fail
+        list, in the caller's job order."""
+        assert batch.is_cuda and batch.is_contiguous()
+        nj = len(jobs)
+        qj = (runtime.QJob * max(1, nj))()
+        for j, (off, ln, pat) in enumerate(jobs):
+            qj[j] = runtime.QJob(off, ln, pat, 0)
+        flat = [i for p in patterns for i in p]
+        offs = [0]
+        for p in patterns:
+            offs.append(offs[-1] + len(p))
+        bad = (ctypes.c_int32 * max(1, len(flat)))(*flat)
+        boff = (ctypes.c_int32 * len(offs))(*offs)
+        bm = (ctypes.c_uint64 * max(1, (nj + 63) // 64))()
+        check(lib().gfrs_reconstruct_verify_queue(self._ctx, batch.data_ptr(),
+                                                  qj, nj, bad, boff,
+                                                  len(patterns), bm),
+              "reconstruct_verify_queue")
+        bmn = np.ctypeslib.as_array(bm)
+        bits = np.unpackbits(bmn.view(np.uint8), bitorder="little")[:nj]
         return bits.astype(bool).tolist()
 
     def repair_batch(self, batch, bad_idx, disk_dst, bids, vuids,

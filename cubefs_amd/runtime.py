@@ -52,6 +52,38 @@ class Tactic(ctypes.Structure):
     ]
 
 
+class QJob(ctypes.Structure):
+    """gfrs_qjob: one job of a repair queue."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("pattern", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class QItem(ctypes.Structure):
+    """gfrs_qitem: one (job, step) work item of a queue schedule."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("job", ctypes.c_int32),
+        ("pattern", ctypes.c_int32),
+        ("row_off", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class QBucket(ctypes.Structure):
+    """gfrs_qbucket: one launch of a queue schedule."""
+    _fields_ = [
+        ("g", ctypes.c_int32),
+        ("gm", ctypes.c_int32),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -152,6 +184,15 @@ def lib():
                                         i32p, ctypes.c_int, ctypes.c_int,
                                         i32p, ip, i32p, ip, u8p, ip, u32p,
                                         u32p]
+        L.gfrs_reconstruct_verify_queue.argtypes = [vp, vp,
+                                                    ctypes.POINTER(QJob),
+                                                    ctypes.c_int, i32p, i32p,
+                                                    ctypes.c_int, u64p]
+        L.gfrs_compute_queue_schedule.argtypes = [
+            ctypes.POINTER(Tactic), ctypes.POINTER(QJob), ctypes.c_int, i32p,
+            i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(QItem), u64p, ip, ctypes.POINTER(QBucket), ip,
+            i32p, u8p, i32p, ip]
         _lib = L
     return _lib
 

@@ -259,6 +259,63 @@ int gfrs_reconstruct_verify_batch(gfrs_ctx *ctx, void *base,
                                   int nstripes, const int32_t *bad_idx,
                                   int nbad, uint64_t *fail_bitmap);
 
+/* ---- repair queue (worker_slice_recover.go:804-888, the loop over bids) ----
+ * ShardRecover.repair does not see uniform batches: every bid has its own
+ * size and its own set of failed downloads (:826-840).  A queue is a list
+ * of such jobs over one device buffer, served by a bounded number of
+ * launches and ONE sync: at most 4 * ceil(max_rows / 4) kernel launches
+ * whatever njobs and npat are (max_rows: missing data + m for plain RS, bad
+ * shards + check rows, at most 32, for LRC).
+ *
+ * Pattern p is bad_idx[bad_off[p] .. bad_off[p+1]); bad_off has npat+1
+ * non-decreasing entries starting at 0.  An empty pattern is legal and
+ * means verify only.  jobs, bad_idx, bad_off and fail_bitmap are host
+ * memory; base is a device pointer.
+ *
+ * Queue contract (pinned by tests/test_gpu_queue.py):
+ *  - Per-job result.  For each job j the bytes written and bit j of
+ *    fail_bitmap are exactly what gfrs_reconstruct_verify_batch(ctx,
+ *    base + off, shard_len, <any stride>, 1, pattern...) produces for that
+ *    stripe alone, i.e. the reference's Reconstruct followed by Verify,
+ *    local stripes included.
+ *  - Bit numbering.  Bit j refers to the caller's job order, whatever order
+ *    the engine processes jobs in.  fail_bitmap holds (njobs+63)/64 words.
+ *  - Layout.  No alignment is required of off or shard_len.  Only the bad
+ *    shards of each job are written: nothing between jobs and no surviving
+ *    shard.  Jobs must not overlap (not checked).
+ *  - Validation.  Everything is validated before the first launch, and any
+ *    error returns its code and writes nothing:
+ *      every pattern, used by a job or not, with the codes the batch call
+ *      returns - GFRS_ERR_INVALID_SHARDS for an index out of range (and,
+ *      for LRC, a repeated index), GFRS_ERR_TOO_FEW_SHARDS when more than m
+ *      of the n+m global shards are bad;
+ *      GFRS_ERR_INVALID_SHARDS for njobs <= 0, npat <= 0, a malformed
+ *      bad_off, pattern outside [0, npat) or reserved != 0;
+ *      GFRS_ERR_SHARD_NO_DATA for shard_len == 0.
+ *  - Blocking.  The call blocks until the bitmap is ready, like
+ *    gfrs_reconstruct_verify_batch; it runs on the context stream and takes
+ *    the context mutex once.
+ *  - Slow patterns.  LRC tactics outside the single-pass budget (m + l > 4
+ *    or n + m + l > 16) and LRC patterns whose plan needs more than 32 rows
+ *    have no single-pass plan.  Their jobs run one at a time after the queue
+ *    launches, as reconstruct + verify on the same stream: correct, but two
+ *    data passes and several launches per job.
+ *  - A job shorter than a 4096-byte tile still occupies a whole tile of the
+ *    kernel (small jobs are not packed together). */
+typedef struct gfrs_qjob {
+  uint64_t off;       /* shard 0 of this job at base + off; shard i at
+                         base + off + i*shard_len (ec.Buffer layout) */
+  uint64_t shard_len; /* > 0, any value, no alignment */
+  int32_t pattern;    /* 0 <= pattern < npat */
+  int32_t reserved;   /* must be 0 */
+} gfrs_qjob;
+
+int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
+                                  const gfrs_qjob *jobs, int njobs,
+                                  const int32_t *bad_idx,
+                                  const int32_t *bad_off, int npat,
+                                  uint64_t *fail_bitmap);
+
 /* ---- incremental parity (reedsolomon.go:631-668 EncodeIdx) ----
  * Adds data shard idx's contribution into the m parity shards:
  * parity[r] ^= coeff[r][idx]*data.  Parity must be zeroed before the
@@ -329,6 +386,35 @@ int gfrs_compute_plan(const gfrs_tactic *t, int kind, const int32_t *bad,
                       int nbad, int cap, int32_t *in, int *nin, int32_t *out,
                       int *nout, uint8_t *rows, int *rowk, uint32_t *cmp_mask,
                       uint32_t *colpack);
+/* GPU-free: the launch schedule gfrs_reconstruct_verify_queue would build
+ * for a queue, with the same builder, so CPU tests can check it without a
+ * device.  A job whose pattern has nout plan rows runs ceil(nout/4) steps;
+ * all (job, step) pairs with the same step index g and row count gm form one
+ * bucket = one kernel launch.  Bucket b owns items[first, first+count),
+ * ordered by pattern, and the count+1 exclusive prefix sums of
+ * ceil(shard_len/4096) at tile_prefix[first + b ...].  pat_nout / pat_slow
+ * have npat entries, slow_jobs njobs; items holds item_cap entries,
+ * tile_prefix item_cap + bucket_cap, buckets bucket_cap (GFRS_ERR_NOMEM when
+ * the schedule is larger).  Returns the validation codes of the queue call. */
+typedef struct gfrs_qitem {
+  uint64_t off, shard_len; /* of the job */
+  int32_t job;             /* caller's index */
+  int32_t pattern;
+  int32_t row_off;         /* first plan row of this step, 4*g */
+  int32_t reserved;
+} gfrs_qitem;
+typedef struct gfrs_qbucket {
+  int32_t g, gm, first, count;
+} gfrs_qbucket;
+int gfrs_compute_queue_schedule(const gfrs_tactic *t, const gfrs_qjob *jobs,
+                                int njobs, const int32_t *bad_idx,
+                                const int32_t *bad_off, int npat,
+                                int item_cap, int bucket_cap,
+                                gfrs_qitem *items, uint64_t *tile_prefix,
+                                int *nitems, gfrs_qbucket *buckets,
+                                int *nbuckets, int32_t *pat_nout,
+                                uint8_t *pat_slow, int32_t *slow_jobs,
+                                int *nslow);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);

@@ -1,0 +1,186 @@
+"""Repair-queue probe: gfrs_reconstruct_verify_queue against what a caller
+had before it, RS(12+4), wall time of the blocking calls.
+
+ (a) uniform  512 jobs x 4 MiB, one pattern [1]: the queue vs ONE
+     gfrs_reconstruct_verify_batch over the same buffer.
+ (b) mixed    4096 jobs, lengths drawn from {64 KiB, 1 MiB, 4 MiB}, 8
+     patterns: the queue vs a loop of single-job batch calls (nstripes = 1),
+     the only gather-free alternative without the queue.
+ (c) small    65536 jobs x 2 KiB, one pattern: the queue vs the same loop
+     (what the missing small-job packing costs).
+
+(a) runs on random data with encoded parity; (b) and (c) on a zeroed buffer
+(a valid stripe: zero parity), since the kernels' work does not depend on
+the data.  One JSON line on stdout; --out also writes it to a file.
+"""
+import argparse
+import ctypes
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch  # noqa: E402
+from cubefs_amd import codemode, ec, runtime  # noqa: E402
+
+KIB, MIB = 1 << 10, 1 << 20
+PATTERNS = [[1], [], [0, 13], [2, 5, 11, 15], [12], [3, 7], [4, 14, 15], [9]]
+
+
+def timed(fn, reps):
+    fn()                                    # warm-up: plans, buffers
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return {"median_ms": round(statistics.median(out), 3),
+            "min_ms": round(min(out), 3), "max_ms": round(max(out), 3),
+            "reps": reps}
+
+
+class Probe:
+    def __init__(self):
+        self.t = codemode.get_tactic("EC12P4")
+        self.enc = ec.Encoder(self.t)
+        self.L = runtime.lib()
+        self.total = self.t.N + self.t.M
+
+    def args(self, jobs, patterns):
+        qj = (runtime.QJob * len(jobs))()
+        for j, (off, ln, pat) in enumerate(jobs):
+            qj[j] = runtime.QJob(off, ln, pat, 0)
+        flat = [i for p in patterns for i in p] or [0]
+        offs = [0]
+        for p in patterns:
+            offs.append(offs[-1] + len(p))
+        self.bads = [((ctypes.c_int32 * max(1, len(p)))(*p), len(p))
+                     for p in patterns]
+        return (qj, len(jobs), (ctypes.c_int32 * len(flat))(*flat),
+                (ctypes.c_int32 * len(offs))(*offs), len(patterns),
+                (ctypes.c_uint64 * ((len(jobs) + 63) // 64))())
+
+    def queue(self, buf, qargs):
+        rc = self.L.gfrs_reconstruct_verify_queue(self.enc._ctx,
+                                                  buf.data_ptr(), *qargs)
+        assert rc == 0, rc
+        assert not any(qargs[-1]), "verify failed"
+
+    def loop(self, buf, jobs):
+        bm = (ctypes.c_uint64 * 1)()
+        base = buf.data_ptr()
+        call = self.L.gfrs_reconstruct_verify_batch
+        ctx = self.enc._ctx
+        for off, ln, pat in jobs:
+            bad, nbad = self.bads[pat]
+            rc = call(ctx, base + off, ln, self.total * ln, 1, bad, nbad, bm)
+            assert rc == 0 and bm[0] == 0, (rc, bm[0])
+
+    def layout(self, lens, npat, seed=1):
+        rng = random.Random(seed)
+        jobs, off = [], 0
+        for ln in lens:
+            jobs.append((off, ln, rng.randrange(npat)))
+            off += self.total * ln
+        return jobs, off
+
+    def uniform(self, njobs, slen, reps):
+        jobs, nbytes = self.layout([slen] * njobs, 1)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        for lo in range(0, nbytes, 1 << 30):
+            part = buf[lo:lo + (1 << 30)]
+            part.copy_(torch.randint(0, 256, (part.numel(),),
+                                     dtype=torch.uint8, device="cuda"))
+        stride = self.total * slen
+        rc = self.L.gfrs_encode_batch(self.enc._ctx, buf.data_ptr(), slen,
+                                      stride, njobs)
+        assert rc == 0, rc
+        self.enc.synchronize()
+        qargs = self.args(jobs, PATTERNS[:1])
+        bad, nbad = self.bads[0]
+        bm = (ctypes.c_uint64 * ((njobs + 63) // 64))()
+
+        def batch():
+            rc = self.L.gfrs_reconstruct_verify_batch(
+                self.enc._ctx, buf.data_ptr(), slen, stride, njobs, bad,
+                nbad, bm)
+            assert rc == 0 and not any(bm), rc
+
+        # interleave the two so that drift hits both alike
+        res = {"njobs": njobs, "shard_len": slen,
+               "batch_1": timed(batch, reps),
+               "queue_1": timed(lambda: self.queue(buf, qargs), reps),
+               "batch_2": timed(batch, reps),
+               "queue_2": timed(lambda: self.queue(buf, qargs), reps)}
+        b = min(res["batch_1"]["median_ms"], res["batch_2"]["median_ms"])
+        q = min(res["queue_1"]["median_ms"], res["queue_2"]["median_ms"])
+        res["queue_over_batch"] = round(q / b, 4)
+        res["moved_GB"] = round(njobs * slen * (self.t.N + 1) / 1e9, 3)
+        return res
+
+    def versus_loop(self, lens, npat, reps, loop_reps):
+        jobs, nbytes = self.layout(lens, npat)
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        qargs = self.args(jobs, PATTERNS[:npat])
+        res = {"njobs": len(jobs), "bytes": nbytes, "npat": npat,
+               "queue": timed(lambda: self.queue(buf, qargs), reps),
+               "loop": timed(lambda: self.loop(buf, jobs), loop_reps)}
+        res["loop_over_queue"] = round(res["loop"]["median_ms"] /
+                                       res["queue"]["median_ms"], 2)
+        if len(set(lens)) == 1 and npat == 1:
+            # a uniform queue is also one batch call, which packs sub-2 KiB
+            # stripes into shared tiles: the price of the unpacked queue
+            bad, nbad = self.bads[0]
+            bm = (ctypes.c_uint64 * ((len(jobs) + 63) // 64))()
+
+            def batch():
+                rc = self.L.gfrs_reconstruct_verify_batch(
+                    self.enc._ctx, buf.data_ptr(), lens[0],
+                    self.total * lens[0], len(jobs), bad, nbad, bm)
+                assert rc == 0 and not any(bm), rc
+
+            res["batch"] = timed(batch, reps)
+            res["queue_over_batch"] = round(res["queue"]["median_ms"] /
+                                            res["batch"]["median_ms"], 2)
+        return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--scale", type=int, default=1,
+                    help="divide every job count by this (dry runs)")
+    ap.add_argument("--only", default="abc",
+                    help="which configurations to run, e.g. 'ac'")
+    a = ap.parse_args()
+    p = Probe()
+    out = {"device": torch.cuda.get_device_name(0), "tactic": "EC12P4",
+           "scale": a.scale}
+    for name in ("GFRS_RS_SEQ", "GFRS_RS_GRID"):
+        if name in os.environ:
+            out[name] = os.environ[name]
+    if "a" in a.only:
+        out["a_uniform"] = p.uniform(512 // a.scale, 4 * MIB, reps=7)
+        torch.cuda.empty_cache()
+    if "b" in a.only:
+        rng = random.Random(7)
+        lens = [rng.choice([64 * KIB, MIB, 4 * MIB])
+                for _ in range(4096 // a.scale)]
+        out["b_mixed"] = p.versus_loop(lens, 8, reps=5, loop_reps=3)
+        torch.cuda.empty_cache()
+    if "c" in a.only:
+        out["c_small"] = p.versus_loop([2 * KIB] * (65536 // a.scale), 1,
+                                       reps=5, loop_reps=2)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
