@@ -231,6 +231,8 @@ struct gfrs_ctx_impl {
   PinBuf stage_pin;
   DevBuf queue_buf; /* repair queue: pattern descriptors, work items, tile
                        prefix sums of one call */
+  DevBuf repair_buf; /* repair-image queue: descriptors, work items, frame
+                        prefix sums, image table of one call */
 
   /* finalize-pipeline resources (repair path): shard_finalize of chunk i
    * runs on aux_stream behind an event while chunk i+1's repair kernel
@@ -1305,23 +1307,24 @@ int gfrs_reconstruct_verify_batch(gfrs_ctx *ctx, void *base,
 /* The repair queue: per-job erasure pattern and shard length, a bounded
  * number of launches, one sync.  gfrs_plan.cpp validates the patterns,
  * builds their plans (cached here like the batch call's, same namespaces)
- * and decides which job runs in which launch; this function uploads the
- * schedule and issues it.  Jobs of slow patterns follow as the two passes
+ * and decides which job runs in which launch; rv_queue_prepare collects
+ * that and rv_queue_issue uploads the schedule and issues it, both with the
+ * context lock held.  Jobs of slow patterns follow as the two passes
  * gfrs_reconstruct_verify_batch falls back to, without its locks and sync. */
-int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
-                                  const gfrs_qjob *jobs, int njobs,
-                                  const int32_t *bad_idx,
-                                  const int32_t *bad_off, int npat,
-                                  uint64_t *fail_bitmap) {
-  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+struct RvQueue {
+  QueueSchedule sched;
+  std::vector<uint8_t> blob; /* [npat descriptors | work items | tile prefix
+                                sums]; alive until the stream is synced */
+  size_t o_items = 0, o_prefix = 0;
+};
+
+/* Everything that can refuse: nothing is launched, nothing written. */
+static int rv_queue_prepare(gfrs_ctx_impl *c, const gfrs_qjob *jobs, int njobs,
+                            const int32_t *bad_idx, const int32_t *bad_off,
+                            int npat, RvQueue *q) {
   const Code &cd = c->code;
   const bool lrc = cd.t.l != 0;
-  if (njobs <= 0 || npat <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
-  int rc = queue_offsets_check(bad_off, npat);
-  if (rc != GFRS_OK) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  StreamGuard g(c);
-
+  int rc;
   /* every pattern, used or not: validate, then find or build its plan */
   std::vector<QueuePattern> pats(npat);
   std::vector<DevPlan *> plans(npat, nullptr);
@@ -1336,10 +1339,10 @@ int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
                       &key);
     if (rc != GFRS_OK) return rc;
     auto build = [&](Plan *pl) {
-      QueuePattern q;
-      int brc = queue_pattern(cd, bad, nbad, pl, &q);
+      QueuePattern qp;
+      int brc = queue_pattern(cd, bad, nbad, pl, &qp);
       /* the batch call's fallback signal; cached_plan caches no failure */
-      return brc == GFRS_OK && q.slow ? int(GFRS_ERR_UNSUPPORTED) : brc;
+      return brc == GFRS_OK && qp.slow ? int(GFRS_ERR_UNSUPPORTED) : brc;
     };
     rc = cached_plan(c, c->dec_cache, key, c->stream, std::ref(build),
                      &plans[p]);
@@ -1350,37 +1353,52 @@ int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
     if (rc != GFRS_OK) return rc;
     pats[p].nout = plans[p]->nout;
   }
-  QueueSchedule sched;
+  QueueSchedule &sched = q->sched;
   if ((rc = queue_schedule(jobs, njobs, pats.data(), npat, &sched)) != GFRS_OK)
     return rc;
 
   /* one upload: [npat descriptors | work items | tile prefix sums] */
-  const size_t o_items = size_t(npat) * sizeof(QueuePat);
-  const size_t o_prefix = o_items + sched.items.size() * sizeof(gfrs_qitem);
-  const size_t nbytes = o_prefix + sched.tile_prefix.size() * 8;
-  std::vector<uint8_t> blob(nbytes);
+  q->o_items = size_t(npat) * sizeof(QueuePat);
+  q->o_prefix = q->o_items + sched.items.size() * sizeof(gfrs_qitem);
+  const size_t nbytes = q->o_prefix + sched.tile_prefix.size() * 8;
+  q->blob.assign(nbytes, 0);
   for (int p = 0; p < npat; p++) {
     QueuePat d{};
     if (plans[p])
       d = QueuePat{plans[p]->in(), plans[p]->out(), plans[p]->tab(),
                    plans[p]->cmp_mask, plans[p]->nout};
-    memcpy(&blob[size_t(p) * sizeof(QueuePat)], &d, sizeof(d));
+    memcpy(&q->blob[size_t(p) * sizeof(QueuePat)], &d, sizeof(d));
   }
   if (!sched.items.empty()) {
-    memcpy(&blob[o_items], sched.items.data(), o_prefix - o_items);
-    memcpy(&blob[o_prefix], sched.tile_prefix.data(), nbytes - o_prefix);
+    memcpy(&q->blob[q->o_items], sched.items.data(), q->o_prefix - q->o_items);
+    memcpy(&q->blob[q->o_prefix], sched.tile_prefix.data(),
+           nbytes - q->o_prefix);
   }
-  if ((rc = c->queue_buf.ensure(nbytes)) != GFRS_OK) return rc;
-  if ((rc = fail_begin(&c->fail_buf, njobs, c->stream)) != GFRS_OK) return rc;
-  /* blob stays alive until fail_finish has synchronized the stream */
-  HIP_TRY(hipMemcpyAsync(c->queue_buf.p, blob.data(), nbytes,
+  return c->queue_buf.ensure(nbytes);
+}
+
+/* Upload and launch a prepared queue.  Job j reports to fail[j], or to
+ * fail[fail_slot[j]] when the queue is a part of a larger one (q's items are
+ * rewritten for that).  A failure may leave work in flight that still reads
+ * q->blob: the caller synchronizes the stream before it lets go of q. */
+static int rv_queue_issue(gfrs_ctx_impl *c, void *base, RvQueue *q,
+                          const gfrs_qjob *jobs, const int32_t *bad_idx,
+                          const int32_t *bad_off, uint32_t *fail,
+                          const int32_t *fail_slot) {
+  const Code &cd = c->code;
+  const QueueSchedule &sched = q->sched;
+  if (fail_slot) {
+    gfrs_qitem *hi = reinterpret_cast<gfrs_qitem *>(&q->blob[q->o_items]);
+    for (size_t i = 0; i < sched.items.size(); i++)
+      hi[i].job = fail_slot[sched.items[i].job];
+  }
+  HIP_TRY(hipMemcpyAsync(c->queue_buf.p, q->blob.data(), q->blob.size(),
                          hipMemcpyHostToDevice, c->stream));
   const uint8_t *dq = (const uint8_t *)c->queue_buf.p;
-  uint32_t *fail = (uint32_t *)c->fail_buf.p;
   for (const QueueBucket &b : sched.buckets)
     launch_rs_apply_queue(
-        (uint64_t)base, (const gfrs_qitem *)(dq + o_items) + b.first,
-        (const uint64_t *)(dq + o_prefix) + b.prefix, uint32_t(b.count),
+        (uint64_t)base, (const gfrs_qitem *)(dq + q->o_items) + b.first,
+        (const uint64_t *)(dq + q->o_prefix) + b.prefix, uint32_t(b.count),
         sched.tile_prefix[b.prefix + b.count], (const QueuePat *)dq, cd.t.n,
         b.gm, fail, c->stream);
   for (int32_t j : sched.slow_jobs) {
@@ -1390,15 +1408,172 @@ int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
     std::vector<uint8_t> present(cd.total, 1);
     for (int i = 0; i < nbad; i++) present[bad[i]] = 0;
     const Shards sh = strided((const uint8_t *)base + jb.off, 0);
-    rc = reconstruct_all(c, view_of(c), present, jb.shard_len, 1,
-                         /*data_only=*/0, sh);
-    if (rc != GFRS_OK) break;
-    run_encode_plans(OP_VERIFY, c, sh, jb.shard_len, 1, c->stream, fail + j);
+    int rc = reconstruct_all(c, view_of(c), present, jb.shard_len, 1,
+                             /*data_only=*/0, sh);
+    if (rc != GFRS_OK) return rc;
+    run_encode_plans(OP_VERIFY, c, sh, jb.shard_len, 1, c->stream,
+                     fail + (fail_slot ? fail_slot[j] : j));
   }
   hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("reconstruct_verify_queue launch", e);
+  return GFRS_OK;
+}
+
+int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
+                                  const gfrs_qjob *jobs, int njobs,
+                                  const int32_t *bad_idx,
+                                  const int32_t *bad_off, int npat,
+                                  uint64_t *fail_bitmap) {
+  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+  if (njobs <= 0 || npat <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
+  int rc = queue_offsets_check(bad_off, npat);
+  if (rc != GFRS_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+  RvQueue q; /* alive until fail_finish has synchronized the stream */
+  if ((rc = rv_queue_prepare(c, jobs, njobs, bad_idx, bad_off, npat, &q)) !=
+      GFRS_OK)
+    return rc;
+  if ((rc = fail_begin(&c->fail_buf, njobs, c->stream)) != GFRS_OK) return rc;
+  rc = rv_queue_issue(c, base, &q, jobs, bad_idx, bad_off,
+                      (uint32_t *)c->fail_buf.p, nullptr);
+  if (rc != GFRS_OK) {
+    hipStreamSynchronize(c->stream); /* the blob is still being read */
+    return rc;
+  }
+  return fail_finish(&c->fail_buf, njobs, c->stream, fail_bitmap);
+}
+
+/* The repair-image queue: gfrs_repair_batch per job, as one call.  Fused
+ * patterns run the fused frame kernel over their cached plan (namespace 61,
+ * shared with gfrs_repair_batch); in-place patterns are reconstructed and
+ * verified in `base` by the reconstruct queue above (its plans, its
+ * schedule), then framed from `base` by identity work items.  gfrs_plan.cpp
+ * classes the patterns and builds the schedule; this function validates,
+ * uploads one blob and issues: in-place work, the <= 4 frame buckets, the
+ * finalize launch, one fail_finish. */
+int gfrs_repair_queue(gfrs_ctx *ctx, void *base, const gfrs_rjob *jobs,
+                      int njobs, const int32_t *bad_idx,
+                      const int32_t *bad_off, int npat, void *disk_dst,
+                      int64_t block_len, const uint64_t *bids,
+                      const uint64_t *vuids, uint64_t *fail_bitmap) {
+  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+  const Code &cd = c->code;
+  if (njobs <= 0 || npat <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
+  int rc = queue_offsets_check(bad_off, npat);
+  if (rc != GFRS_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+
+  /* every pattern, used or not: validate and class it; fused ones find or
+   * build their plan */
+  std::vector<RepairPattern> pats(npat);
+  std::vector<DevPlan *> plans(npat, nullptr);
+  for (int p = 0; p < npat; p++) {
+    const int32_t *bad = bad_idx + bad_off[p];
+    const int nbad = bad_off[p + 1] - bad_off[p];
+    if ((rc = repair_pattern_check(cd, bad, nbad, &pats[p])) != GFRS_OK)
+      return rc;
+    if (pats[p].cls != GFRS_RPAT_FUSED) continue;
+    PlanKey key;
+    rc = bad_list_key(61, bad, nbad, cd.total, /*dup_ok=*/false, &key);
+    if (rc != GFRS_OK) return rc;
+    auto build = [&](Plan *pl) { return plan_fused_repair(cd, bad, nbad, pl); };
+    rc = cached_plan(c, c->dec_cache, key, c->stream, std::ref(build),
+                     &plans[p]);
+    if (rc != GFRS_OK) return rc;
+    pats[p].gm = plans[p]->nout;
+  }
+  if (block_len != REPAIR_BLOCK) return GFRS_ERR_UNSUPPORTED;
+  RepairSchedule sched;
+  rc = repair_schedule(jobs, njobs, pats.data(), npat, bad_idx, bad_off,
+                       (uint64_t)disk_dst, bids, vuids, &sched);
+  if (rc != GFRS_OK) return rc;
+
+  /* the in-place jobs as a reconstruct queue of their own: their patterns
+   * compacted, each job reporting to its caller index */
+  RvQueue rvq;
+  std::vector<gfrs_qjob> ijobs;
+  std::vector<int32_t> ibad, ioff(1, 0), ipat(npat, -1);
+  if (!sched.inplace_jobs.empty()) {
+    for (int p = 0; p < npat; p++) {
+      if (pats[p].cls == GFRS_RPAT_FUSED) continue;
+      ipat[p] = int32_t(ioff.size()) - 1;
+      ibad.insert(ibad.end(), bad_idx + bad_off[p], bad_idx + bad_off[p + 1]);
+      ioff.push_back(int32_t(ibad.size()));
+    }
+    for (int32_t j : sched.inplace_jobs)
+      ijobs.push_back(
+          gfrs_qjob{jobs[j].off, jobs[j].shard_len, ipat[jobs[j].pattern], 0});
+    rc = rv_queue_prepare(c, ijobs.data(), int(ijobs.size()), ibad.data(),
+                          ioff.data(), int(ioff.size()) - 1, &rvq);
+    if (rc != GFRS_OK) return rc;
+  }
+
+  /* ONE blob: [npat + total descriptors | identity indices | identity table
+   * | work items | frame prefix sums | image table]; identity descriptors
+   * point into the blob itself */
+  const int ndesc = npat + cd.total;
+  const size_t o_ident = size_t(ndesc) * sizeof(RepairDesc);
+  const size_t o_tab = (o_ident + size_t(cd.total) * 4 + 15) / 16 * 16;
+  const size_t o_items = o_tab + 32;
+  const size_t o_prefix = o_items + sched.items.size() * sizeof(gfrs_ritem);
+  const size_t o_imgs = o_prefix + sched.frame_prefix.size() * 8;
+  const size_t nbytes = o_imgs + sched.images.size() * sizeof(gfrs_rimage);
+  if ((rc = c->repair_buf.ensure(nbytes)) != GFRS_OK) return rc;
+  const uint8_t *dq = (const uint8_t *)c->repair_buf.p;
+  std::vector<uint8_t> blob(nbytes, 0);
+  for (int p = 0; p < npat; p++) {
+    if (!plans[p]) continue;
+    const RepairDesc d{plans[p]->in(), plans[p]->tab(), plans[p]->k,
+                       pats[p].nw, pats[p].colpack, 0};
+    memcpy(&blob[size_t(p) * sizeof(RepairDesc)], &d, sizeof(d));
+  }
+  for (int s = 0; s < cd.total; s++) {
+    const RepairDesc d{(const int32_t *)(dq + o_ident) + s, dq + o_tab, 1, 1,
+                       0, 0};
+    memcpy(&blob[size_t(npat + s) * sizeof(RepairDesc)], &d, sizeof(d));
+    const int32_t idx = s;
+    memcpy(&blob[o_ident + size_t(s) * 4], &idx, 4);
+  }
+  { /* coefficient 1 in the A|B|C split of DevPlan::upload */
+    uint8_t *lt = &blob[o_tab];
+    for (int i = 0; i < 8; i++) {
+      lt[i] = uint8_t(i);
+      lt[8 + i] = uint8_t(8 * i);
+    }
+    for (int i = 0; i < 4; i++) lt[16 + i] = uint8_t(64 * i);
+  }
+  memcpy(&blob[o_items], sched.items.data(), o_prefix - o_items);
+  memcpy(&blob[o_prefix], sched.frame_prefix.data(), o_imgs - o_prefix);
+  memcpy(&blob[o_imgs], sched.images.data(), nbytes - o_imgs);
+
+  if ((rc = fail_begin(&c->fail_buf, njobs, c->stream)) != GFRS_OK) return rc;
+  uint32_t *fail = (uint32_t *)c->fail_buf.p;
+  /* both blobs stay alive until the stream has been synchronized */
+  if (!ijobs.empty())
+    rc = rv_queue_issue(c, base, &rvq, ijobs.data(), ibad.data(), ioff.data(),
+                        fail, sched.inplace_jobs.data());
+  hipError_t e = hipSuccess;
+  if (rc == GFRS_OK)
+    e = hipMemcpyAsync(c->repair_buf.p, blob.data(), nbytes,
+                       hipMemcpyHostToDevice, c->stream);
+  if (rc == GFRS_OK && e == hipSuccess) {
+    for (const RepairBucket &b : sched.buckets)
+      launch_rs_repair_frame_queue(
+          (uint8_t *)disk_dst, (uint64_t)base,
+          (const gfrs_ritem *)(dq + o_items) + b.first,
+          (const uint64_t *)(dq + o_prefix) + b.prefix, uint32_t(b.count),
+          sched.frame_prefix[b.prefix + b.count], (const RepairDesc *)dq,
+          cd.t.n, b.gm, fail, c->stream);
+    launch_shard_finalize_queue((uint8_t *)disk_dst,
+                                (const gfrs_rimage *)(dq + o_imgs),
+                                int(sched.images.size()), c->stream);
+    e = hipGetLastError();
+  }
   if (rc != GFRS_OK || e != hipSuccess) {
-    hipStreamSynchronize(c->stream); /* blob is still being read */
-    return rc != GFRS_OK ? rc : hip_fail("reconstruct_verify_queue launch", e);
+    hipStreamSynchronize(c->stream); /* the blobs are still being read */
+    return rc != GFRS_OK ? rc : hip_fail("repair_queue launch", e);
   }
   return fail_finish(&c->fail_buf, njobs, c->stream, fail_bitmap);
 }

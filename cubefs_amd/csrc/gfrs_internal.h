@@ -122,6 +122,35 @@ void launch_rs_apply_queue(uint64_t base, const gfrs_qitem *items,
                            uint64_t total_tiles, const QueuePat *pats, int k,
                            int gm, uint32_t *fail, hipStream_t s);
 
+/* Repair-image queue: one bucket of the repair schedule (gfrs_plan.h), i.e.
+ * every work item whose descriptor carries gm rows.  An item is the fused
+ * repair of launch_rs_repair_frame over its own job:
+ *   shard i at base + item.off + i * item.shard_len,
+ *   body of image column c at dst + item.img + c * item.img_stride + 32,
+ * under descs[item.desc] (device pointers into the cached DevPlans, or into
+ * the call's blob for identity descriptors).  frame_prefix holds the
+ * nitems+1 exclusive prefix sums of ceil(shard_len / 65532), total_frames
+ * its last entry; kmax bounds every descriptor's k (it sizes the LDS
+ * tables).  Mismatches of check rows are ORed into fail[item.job]. */
+struct RepairDesc {
+  const int32_t *imap; /* k inputs then gm - nw check shards */
+  const uint8_t *tabs; /* [gm*k][32] */
+  int32_t k, nw;
+  uint32_t colpack;
+  int32_t reserved;
+};
+void launch_rs_repair_frame_queue(uint8_t *dst, uint64_t base,
+                                  const gfrs_ritem *items,
+                                  const uint64_t *frame_prefix,
+                                  uint32_t nitems, uint64_t total_frames,
+                                  const RepairDesc *descs, int kmax, int gm,
+                                  uint32_t *fail, hipStream_t s);
+/* Headers and footers of every image of a repair queue: launch_shard_finalize
+ * with the image's place, raw size and ids read from imgs[]; block_len is
+ * 65536. */
+void launch_shard_finalize_queue(uint8_t *dst, const gfrs_rimage *imgs,
+                                 int nimg, hipStream_t s);
+
 /* EncodeIdx-style accumulate apply (reedsolomon.go:631-668):
  * out[r] ^= coeff[r]*in for one input shard. */
 void launch_rs_apply_xor(const uint64_t *ptrs, int nptr,

@@ -3106,6 +3106,371 @@ void launch_rs_repair_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
 #undef GFRS_RP_GO
 }
 
+/* Repair-image queue: rs_repair_frame_k over the work items of one bucket of
+ * the repair schedule (gfrs_plan.h).  The math of a frame - the 16 KiB
+ * passes, the op-chain register CRC, the LDS-staged tail bytes, the per-row
+ * write or compare, the ballot fail flag, the frame header store - is the
+ * batch kernel's; what differs is where a frame comes from:
+ *  - the grid is capped and block b walks the CONTIGUOUS frame range
+ *    [b*per_blk, (b+1)*per_blk) of the bucket.  frame -> work item: one
+ *    binary search over the frame prefix sums at the block's first frame,
+ *    then a forward walk (every item has >= 1 frame).  All of it depends on
+ *    blockIdx and kernel arguments only, so the search, the item and its
+ *    descriptor are scalar loads, as in rs_apply_queue_k;
+ *  - the tables (ctab) are restaged into LDS, and imap, k, nw and colpack
+ *    reloaded, only when the descriptor of the next frame differs from what
+ *    is loaded, between two barriers.  The test is block-uniform and no lane
+ *    leaves the loop body early, so every lane reaches every barrier;
+ *  - every pointer is rebuilt from base + item.off; a block works on one job
+ *    at a time, so the fail flag goes to fail[item.job];
+ *  - cross-frame prefetch: the batch kernel computes the next frame's unit 0
+ *    from the CURRENT imap[0], shard_len and stripe arithmetic.  Here the
+ *    next frame may belong to another job or descriptor, so its address and
+ *    length come from the NEXT item's own values (its off, shard_len and its
+ *    descriptor's imap[0]); `pref` says that vnext holds exactly the loads
+ *    the top of the next frame would issue, otherwise the top reloads.  No
+ *    load ever leaves the shards of the job it belongs to;
+ *  - jobs of at most 4096 bytes run here too, one short frame per block (no
+ *    wave-per-stripe packing). */
+template <int GM, int WPS = 4>
+__global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_repair_frame_queue_k(
+    uint8_t *__restrict__ dst /* disk_dst */, uint64_t base,
+    const gfrs_ritem *__restrict__ items,
+    const uint64_t *__restrict__ frame_prefix, uint32_t nitems,
+    uint64_t total_frames, const RepairDesc *__restrict__ descs,
+    uint32_t *__restrict__ fail) {
+  constexpr int EF_PASS = 16384;
+  constexpr int EF_PASSES = 4;
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+
+  const uint64_t per_blk = (total_frames + gridDim.x - 1) / gridDim.x;
+  const uint64_t f_lo = uint64_t(blockIdx.x) * per_blk;
+  const uint64_t f_hi =
+      f_lo + per_blk < total_frames ? f_lo + per_blk : total_frames;
+  if (f_lo >= f_hi) return; /* whole block, before any barrier */
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t(*tab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem);
+  uint32_t(*stab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem + 8192);
+  uint32_t *red = reinterpret_cast<uint32_t *>(smem + 12288);
+  uint32_t *x8tab = reinterpret_cast<uint32_t *>(smem + 12288 + EF_RED);
+  uint8_t *tailb = smem + 12288 + EF_RED + 64;
+  uint8_t *ctab = smem + 12288 + EF_RED + 64 + 256;
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift4k[0][0])[i];
+  if (threadIdx.x == 0) {
+    uint32_t v = 0x80000000u;
+    for (int j = 0; j < 16; j++) {
+      x8tab[j] = v;
+      v = gf2_mulmod_d(v, g_pow8[0]);
+    }
+  }
+  const int64_t lane16 = int64_t(threadIdx.x) * 16;
+  const int lane16i = int(threadIdx.x) * 16;
+  constexpr uint32_t INV16K = 0x479933FCu;
+  const uint32_t op_pA =
+      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16 + 16)));
+  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
+  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
+  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  const uint32_t it_full =
+      gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
+  __syncthreads();
+
+  /* largest it with frame_prefix[it] <= f_lo (frame_prefix[0] == 0) */
+  uint32_t it = 0;
+  for (uint32_t hi = nitems; hi - it > 1;) {
+    const uint32_t mid = it + (hi - it) / 2;
+    if (frame_prefix[mid] <= f_lo)
+      it = mid;
+    else
+      hi = mid;
+  }
+
+  /* imap arrives as a pointer read from the descriptor table: the constant
+   * address space keeps its (block-uniform) reads scalar, as they are in
+   * rs_repair_frame_k where imap is a kernel argument */
+  typedef const __attribute__((address_space(4))) int32_t *IdxList;
+  int cur_desc = -1;
+  IdxList imap = nullptr;
+  int k = 0, nw = 0;
+  uint32_t colpack = 0;
+  uint4 vnext[4] = {uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0},
+                    uint4{0, 0, 0, 0}};
+  bool pref = false; /* vnext = pass 0, unit 0 of the frame about to start */
+
+  for (uint64_t fr = f_lo; fr < f_hi; fr++) {
+    while (frame_prefix[it + 1] <= fr) it++; /* it + 1 <= nitems */
+    const gfrs_ritem item = items[it];
+    const size_t shard_len = item.shard_len;
+    const int64_t f = int64_t(fr - frame_prefix[it]);
+    if (item.desc != cur_desc) {
+      const RepairDesc d = descs[item.desc];
+      __syncthreads(); /* all lanes are done with the old tables */
+      const uint4 *src =
+          reinterpret_cast<const uint4 *>(as_global(uint64_t(d.tabs)));
+      for (int i = threadIdx.x; i < GM * d.k * 2; i += CRC_BLOCKT)
+        reinterpret_cast<uint4 *>(ctab)[i] = src[i];
+      __syncthreads();
+      cur_desc = item.desc;
+      imap = (IdxList)(uint64_t)d.imap;
+      k = d.k;
+      nw = d.nw;
+      colpack = d.colpack;
+    }
+    const int64_t p0 = f * payload_full;
+    const int64_t payload = i64min(payload_full, int64_t(shard_len) - p0);
+    const uint8_t *sbase = as_global(base + item.off);
+    /* body of the item's image column 0; column c at + c * img_stride */
+    uint8_t *ibody = dst + item.img + 32;
+
+    uint4 acc[GM][4];
+    if (!pref) { /* pass 0, unit 0 */
+      const int rb0 = int(i64min(int64_t(EF_PASS), payload));
+      const uint8_t *src0 = sbase + size_t(imap[0]) * shard_len + p0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        vnext[i] = off + 16 <= rb0
+                       ? *reinterpret_cast<const uint4 *>(src0 + off)
+                       : uint4{0, 0, 0, 0};
+      }
+    }
+    pref = false;
+    for (int j = threadIdx.x; j < 64; j += CRC_BLOCKT) red[j] = 0;
+    __syncthreads();
+
+    uint32_t mismatch = 0;
+    for (int h = 0; h < EF_PASSES; h++) {
+      const int64_t r0 = int64_t(h) * EF_PASS;
+      const int64_t rbytes = i64min(int64_t(EF_PASS), payload - r0);
+      if (rbytes <= 0) break;
+#pragma unroll
+      for (int r = 0; r < GM; r++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[r][i] = uint4{0, 0, 0, 0};
+
+      uint32_t op = h == 0   ? op_pA
+                    : h == 1 ? op_pB
+                    : h == 2 ? op_pC
+                             : op_pD;
+      if (h == EF_PASSES - 1 && threadIdx.x == 255)
+        op = shift4k(op, stab);
+      if (payload != payload_full) {
+        int np = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (int64_t(i) * 4096 + lane16 + 16 <= rbytes) np = i + 1;
+        const int64_t end =
+            np ? r0 + int64_t(np - 1) * 4096 + lane16 + 16 : r0;
+        op = x8n_d(uint64_t(payload - end));
+      }
+
+      const int rbi = int(rbytes);
+      for (int c = 0; c < k; c++) {
+        uint4 vcur[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) vcur[i] = vnext[i];
+        if (c + 1 < k) { /* next input's loads fly over this MAC */
+          const uint8_t *nsrc =
+              sbase + size_t(imap[c + 1]) * shard_len + p0 + r0;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            vnext[i] = off + 16 <= rbi
+                           ? *reinterpret_cast<const uint4 *>(nsrc + off)
+                           : uint4{0, 0, 0, 0};
+          }
+        }
+        LinTab lt[GM];
+#pragma unroll
+        for (int r = 0; r < GM; r++) lt[r] = lintab_load(ctab, r * k + c);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int off = i * 4096 + lane16i;
+          if (off + 16 <= rbi) {
+#pragma unroll
+            for (int d = 0; d < 4; d++)
+              gfmac4_lin_rows<GM>(acc, i, d, (&vcur[i].x)[d], lt);
+          }
+        }
+      }
+      { /* prefetch unit 0 of the next pass, or of the next frame */
+        int64_t r0n = r0 + EF_PASS;
+        int64_t rbn = i64min(int64_t(EF_PASS), payload - r0n);
+        const uint8_t *nbase = sbase + size_t(imap[0]) * shard_len + p0 + r0n;
+        if (rbn <= 0 && fr + 1 < f_hi) {
+          /* the frame after this one, from ITS item: the same job's next
+           * frame, or frame 0 of the next item (its own off, shard_len and
+           * its descriptor's first input) */
+          if (frame_prefix[it + 1] <= fr + 1) {
+            const gfrs_ritem nx = items[it + 1];
+            const IdxList nmap = (IdxList)(uint64_t)descs[nx.desc].imap;
+            rbn = i64min(int64_t(EF_PASS), int64_t(nx.shard_len));
+            nbase = as_global(base + nx.off) +
+                    size_t(nmap[0]) * size_t(nx.shard_len);
+          } else {
+            const int64_t p0n = p0 + payload_full;
+            rbn = i64min(int64_t(EF_PASS), int64_t(shard_len) - p0n);
+            nbase = sbase + size_t(imap[0]) * shard_len + p0n;
+          }
+          pref = true;
+        }
+        if (rbn > 0) {
+          const int rbni = int(rbn);
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            vnext[i] = off + 16 <= rbni
+                           ? *reinterpret_cast<const uint4 *>(nbase + off)
+                           : uint4{0, 0, 0, 0};
+          }
+        }
+      }
+      if (rbytes < EF_PASS) { /* stage input tail bytes: lane (c,j) */
+        const int tt0 = (rbi / 16) * 16;
+        const int c2 = int(threadIdx.x) >> 4, j = int(threadIdx.x) & 15;
+        if (c2 < k && tt0 + j < rbi)
+          tailb[c2 * 16 + j] =
+              sbase[size_t(imap[c2]) * shard_len + p0 + r0 + tt0 + j];
+        __syncthreads();
+      }
+#pragma unroll
+      for (int r = 0; r < GM; r++) {
+        if (r < nw) { /* rebuild row: framed image output */
+          const int col = int((colpack >> (4 * r)) & 0xF);
+          uint8_t *fdst = ibody + size_t(col) * item.img_stride +
+                          f * block_len + CRC_LEN + r0;
+          uint32_t t = 0;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            if (off + 16 <= rbi) {
+              uint32_t *dw = reinterpret_cast<uint32_t *>(fdst + off);
+              dw[0] = acc[r][i].x; dw[1] = acc[r][i].y;
+              dw[2] = acc[r][i].z; dw[3] = acc[r][i].w;
+              t = shift4k(t, stab) ^ crc16_reg(acc[r][i], tab);
+            }
+          }
+          uint32_t part = t ? gf2_mulmod_d(op, t) : 0;
+          if (rbytes < EF_PASS) { /* lane-parallel tail (see encode) */
+            const int t0 = (rbi / 16) * 16;
+            const int p = t0 + int(threadIdx.x);
+            if (p < rbi) {
+              uint8_t pv = 0;
+              for (int c2 = 0; c2 < k; c2++) {
+                const uint8_t b2 = tailb[c2 * 16 + (p - t0)];
+                pv ^= gfmul1_lin(ctab + size_t(r * k + c2) * 32, b2);
+              }
+              fdst[p] = pv;
+              part ^= gf2_mulmod_d(x8tab[rbi - 1 - p], tab[0][pv]);
+            }
+          }
+#pragma unroll
+          for (int sh = 32; sh > 0; sh >>= 1)
+            part ^= __shfl_xor(part, sh, 64);
+          if ((threadIdx.x & 63) == 0)
+            red[(threadIdx.x >> 6) * 16 + r] ^= part;
+        } else { /* check row: compare against the surviving parity */
+          const uint8_t *cshard =
+              sbase + size_t(imap[k + (r - nw)]) * shard_len + p0 + r0;
+          uint32_t d = 0;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            if (off + 16 <= rbi) {
+              const uint4 w =
+                  *reinterpret_cast<const uint4 *>(cshard + off);
+              d |= (w.x ^ acc[r][i].x) | (w.y ^ acc[r][i].y) |
+                   (w.z ^ acc[r][i].z) | (w.w ^ acc[r][i].w);
+            }
+          }
+          if (rbytes < EF_PASS) {
+            const int t0 = (rbi / 16) * 16;
+            const int p = t0 + int(threadIdx.x);
+            if (p < rbi) {
+              uint8_t pv = 0;
+              for (int c2 = 0; c2 < k; c2++) {
+                const uint8_t b2 = tailb[c2 * 16 + (p - t0)];
+                pv ^= gfmul1_lin(ctab + size_t(r * k + c2) * 32, b2);
+              }
+              d |= uint32_t(pv ^ cshard[p]);
+            }
+          }
+          mismatch |= d;
+        }
+      }
+    }
+
+    /* fail flag + the 4 B LE frame headers of the rebuilt images */
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1)
+      mismatch |= __shfl_xor(mismatch, sh, 64);
+    __syncthreads();
+    {
+      const int r = int(threadIdx.x);
+      if (r < nw) {
+        const uint32_t itv =
+            payload == payload_full
+                ? it_full
+                : gf2_mulmod_d(x8n_d(uint64_t(payload)), 0xFFFFFFFFu);
+        const int col = int((colpack >> (4 * r)) & 0xF);
+        const uint32_t crc =
+            ~(itv ^ red[r] ^ red[16 + r] ^ red[32 + r] ^ red[48 + r]);
+        *reinterpret_cast<uint32_t *>(ibody + size_t(col) * item.img_stride +
+                                      f * block_len) = crc;
+      }
+    }
+    if ((threadIdx.x & 63) == 0 && mismatch)
+      atomicOr(&fail[item.job], 1u);
+    __syncthreads();
+  }
+}
+
+void launch_rs_repair_frame_queue(uint8_t *dst, uint64_t base,
+                                  const gfrs_ritem *items,
+                                  const uint64_t *frame_prefix,
+                                  uint32_t nitems, uint64_t total_frames,
+                                  const RepairDesc *descs, int kmax, int gm,
+                                  uint32_t *fail, hipStream_t s) {
+  if (nitems == 0 || total_frames == 0) return;
+  /* the cap of fused_grid, read on every launch: GFRS_CRC_GRID forces the
+   * multi-frame walk, the restage and the cross-item prefetch at tiny
+   * shapes */
+  const uint64_t cap = uint64_t(env_grid("GFRS_CRC_GRID", 16384));
+  const int grid = int(total_frames < cap ? total_frames : cap);
+  const int lds = 12288 + EF_RED + 64 + 256 + gm * kmax * 32;
+  /* the wave policy of launch_rs_repair_frame, on the bucket's mean job:
+   * 3 waves/SIMD from about 1 MiB (16 frames) per shard */
+  static const int waves_env = []() {
+    const char *e = getenv("GFRS_RP_WAVES");
+    const int v = e ? atoi(e) : 0;
+    return (v == 3 || v == 4) ? v : 0;
+  }();
+  const int waves =
+      waves_env ? waves_env : (total_frames >= uint64_t(16) * nitems ? 3 : 4);
+#define GFRS_RQ_GO(G, W)                                                   \
+  hipLaunchKernelGGL((rs_repair_frame_queue_k<G, W>), dim3(grid),          \
+                     dim3(CRC_BLOCKT), lds, s, dst, base, items,           \
+                     frame_prefix, nitems, total_frames, descs, fail)
+#define GFRS_RQ_SEL(G)                                                     \
+  do {                                                                     \
+    if (waves == 3) GFRS_RQ_GO(G, 3);                                      \
+    else GFRS_RQ_GO(G, 4);                                                 \
+  } while (0)
+  switch (gm) {
+    case 1: GFRS_RQ_SEL(1); break;
+    case 2: GFRS_RQ_SEL(2); break;
+    case 3: GFRS_RQ_SEL(3); break;
+    default: GFRS_RQ_SEL(4);
+  }
+#undef GFRS_RQ_SEL
+#undef GFRS_RQ_GO
+}
+
 /* Small-shard fused encode+frame: one 64-lane WAVE per stripe, no LDS
  * staging, no barriers (everything wave-local).  Shard <= 4096 B is one
  * short crc32block frame; lane w owns pieces {i*1024 + 16w : i < NI}
@@ -3681,6 +4046,77 @@ void launch_shard_finalize(uint8_t *dst, size_t dst_stride,
   hipLaunchKernelGGL(shard_finalize_k, dim3(blocks), dim3(wps * 64), 0, s,
                      dst, dst_stride, bids, vuids, raw_size, block_len,
                      nshards);
+}
+
+/* shard_finalize_k for a repair queue: one wave per image, its place, raw
+ * size and ids read from the image table (block_len 65536). */
+__global__ void shard_finalize_queue_k(uint8_t *__restrict__ dst,
+                                       const gfrs_rimage *__restrict__ imgs,
+                                       int nimg) {
+  constexpr int64_t block_len = 65536;
+  const int sh = blockIdx.x * (blockDim.x / 64) + (threadIdx.x / 64);
+  const int lane = threadIdx.x & 63;
+  if (sh >= nimg || lane != 0) return;
+  const gfrs_rimage im = imgs[sh];
+  uint8_t *img = dst + im.off;
+  const int64_t raw_size = int64_t(im.size);
+  { /* the 32 B header (shard.go:241-261), big-endian fields */
+    uint32_t w[8];
+    w[1] = 0xccefcdabu; /* ab cd ef cc */
+    w[2] = __builtin_bswap32(uint32_t(im.bid >> 32));
+    w[3] = __builtin_bswap32(uint32_t(im.bid));
+    w[4] = __builtin_bswap32(uint32_t(im.vuid >> 32));
+    w[5] = __builtin_bswap32(uint32_t(im.vuid));
+    w[6] = __builtin_bswap32(uint32_t(raw_size));
+    w[7] = 0;
+    uint32_t c = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 1; i < 8; i++) {
+      const uint32_t x = w[i];
+#pragma unroll
+      for (int b = 0; b < 4; b++)
+        c = g_crc_tab4[0][(c ^ (x >> (8 * b))) & 0xFF] ^ (c >> 8);
+    }
+    w[0] = __builtin_bswap32(~c);
+    uint32_t *d32 = reinterpret_cast<uint32_t *>(img);
+#pragma unroll
+    for (int i = 0; i < 8; i++) d32[i] = w[i];
+  }
+  /* footer CRC: GF(2)-combine the frame CRCs the frame kernel wrote.  The
+   * raw size is per image here, not a kernel argument, so x^(8*plen) would
+   * be a per-lane computation in every iteration: the operator of a full
+   * frame is computed once, only the last frame can need another */
+  const int64_t payload_full = block_len - CRC_LEN;
+  const int64_t nframes = (raw_size + payload_full - 1) / payload_full;
+  const uint32_t op_full = x8n_d(uint64_t(payload_full));
+  uint32_t crc = 0;
+  int64_t remain = raw_size;
+  for (int64_t f = 0; f < nframes; f++) {
+    uint32_t fc;
+    __builtin_memcpy(&fc, img + 32 + f * block_len, 4); /* LE header */
+    const int64_t plen = remain < payload_full ? remain : payload_full;
+    if (f == 0) {
+      crc = fc;
+    } else {
+      const uint32_t op =
+          plen == payload_full ? op_full : x8n_d(uint64_t(plen));
+      crc = gf2_mulmod_d(op, crc) ^ fc;
+    }
+    remain -= plen;
+  }
+  uint8_t *ftr = img + 32 + (raw_size + CRC_LEN * nframes);
+  ftr[0] = 0xcc; ftr[1] = 0xef; ftr[2] = 0xcd; ftr[3] = 0xab;
+  ftr[4] = uint8_t(crc >> 24); ftr[5] = uint8_t(crc >> 16); /* BE */
+  ftr[6] = uint8_t(crc >> 8); ftr[7] = uint8_t(crc);
+}
+
+void launch_shard_finalize_queue(uint8_t *dst, const gfrs_rimage *imgs,
+                                 int nimg, hipStream_t s) {
+  if (nimg <= 0) return;
+  const int wps = 4; /* waves per block */
+  const int blocks = (nimg + wps - 1) / wps;
+  hipLaunchKernelGGL(shard_finalize_queue_k, dim3(blocks), dim3(wps * 64), 0,
+                     s, dst, imgs, nimg);
 }
 
 void launch_shard_parse(const uint8_t *img, size_t stride, int64_t raw_size,

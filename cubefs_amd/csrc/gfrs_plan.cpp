@@ -426,9 +426,185 @@ int queue_schedule(const gfrs_qjob *jobs, int njobs, const QueuePattern *pats,
   return GFRS_OK;
 }
 
+/* ---- the repair-image queue ---- */
+
+int repair_pattern_check(const Code &c, const int32_t *bad, int nbad,
+                         RepairPattern *r) {
+  *r = RepairPattern();
+  if (nbad <= 0 || !bad) return GFRS_ERR_INVALID_SHARDS;
+  std::vector<uint8_t> seen(c.total, 0);
+  int nglobal = 0;
+  for (int i = 0; i < nbad; i++) {
+    if (bad[i] < 0 || bad[i] >= c.total || seen[bad[i]])
+      return GFRS_ERR_INVALID_SHARDS; /* strict for every tactic */
+    seen[bad[i]] = 1;
+    nglobal += bad[i] < c.t.n + c.t.m;
+  }
+  bool slow = false;
+  int rc = queue_pattern_check(c, bad, nbad, &slow);
+  if (rc != GFRS_OK) return rc;
+  r->nbad = nbad;
+  /* the gate of gfrs_repair_batch's fused path */
+  const gfrs_tactic &t = c.t;
+  const bool fused = (t.l == 0 || lrc_single_pass(c)) && t.m >= 1 &&
+                     t.m + t.l <= REPAIR_ROWS && c.total <= 16 &&
+                     nglobal <= t.m && nbad <= REPAIR_ROWS;
+  if (!fused) {
+    r->cls = slow ? GFRS_RPAT_INPLACE_SLOW : GFRS_RPAT_INPLACE;
+    return GFRS_OK;
+  }
+  r->cls = GFRS_RPAT_FUSED;
+  r->nw = nbad;
+  return repair_colpack(c.total, bad, nbad, &r->colpack);
+}
+
+int repair_pattern(const Code &c, const int32_t *bad, int nbad, Plan *p,
+                   RepairPattern *r) {
+  int rc = repair_pattern_check(c, bad, nbad, r);
+  if (rc != GFRS_OK || r->cls != GFRS_RPAT_FUSED) return rc;
+  if ((rc = plan_fused_repair(c, bad, nbad, p)) != GFRS_OK) return rc;
+  r->gm = int(p->out.size());
+  return GFRS_OK;
+}
+
+uint64_t repair_image_size(uint64_t shard_len) {
+  const uint64_t frames = (shard_len - 1) / REPAIR_PAYLOAD + 1;
+  return 32 + shard_len + 4 * frames + 8;
+}
+
+int repair_schedule(const gfrs_rjob *jobs, int njobs,
+                    const RepairPattern *pats, int npat,
+                    const int32_t *bad_idx, const int32_t *bad_off,
+                    uint64_t dst_addr, const uint64_t *bids,
+                    const uint64_t *vuids, RepairSchedule *out) {
+  *out = RepairSchedule();
+  if (njobs <= 0 || npat <= 0 || !jobs || !pats) return GFRS_ERR_INVALID_SHARDS;
+  size_t count[REPAIR_ROWS + 1] = {0}, nimg = 0;
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_rjob &jb = jobs[j];
+    if (jb.pattern < 0 || jb.pattern >= npat || jb.reserved != 0)
+      return GFRS_ERR_INVALID_SHARDS;
+    if (jb.shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
+    if ((dst_addr + jb.img_off) % 4 || jb.img_stride % 4 ||
+        jb.img_stride < repair_image_size(jb.shard_len))
+      return GFRS_ERR_INVALID_SHARDS;
+    const RepairPattern &rp = pats[jb.pattern];
+    if (rp.cls == GFRS_RPAT_FUSED) {
+      if (rp.gm < rp.nbad || rp.gm > REPAIR_ROWS) return GFRS_ERR_UNSUPPORTED;
+      count[rp.gm]++;
+    } else {
+      count[1] += size_t(rp.nbad);
+    }
+    nimg += size_t(rp.nbad);
+  }
+  size_t bucket_of[REPAIR_ROWS + 1], nitems = 0;
+  for (int gm = 1; gm <= REPAIR_ROWS; gm++) {
+    if (!count[gm]) continue;
+    RepairBucket b;
+    b.gm = gm;
+    b.first = nitems;
+    b.count = count[gm];
+    b.prefix = nitems + out->buckets.size();
+    bucket_of[gm] = out->buckets.size();
+    nitems += count[gm];
+    out->buckets.push_back(b);
+  }
+  out->items.reserve(nitems);
+  out->images.reserve(nimg);
+  /* caller order first: bucket by bucket below, a stable sort by descriptor
+   * then leaves the items of one descriptor in caller order */
+  std::vector<std::vector<gfrs_ritem>> per(REPAIR_ROWS + 1);
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_rjob &jb = jobs[j];
+    const RepairPattern &rp = pats[jb.pattern];
+    const int32_t *bad = bad_idx + bad_off[jb.pattern];
+    for (int b = 0; b < rp.nbad; b++) {
+      const size_t id = out->images.size();
+      out->images.push_back(gfrs_rimage{jb.img_off + uint64_t(b) * jb.img_stride,
+                                        jb.shard_len, bids ? bids[id] : 0,
+                                        vuids ? vuids[id] : 0});
+      if (rp.cls != GFRS_RPAT_FUSED)
+        per[1].push_back(gfrs_ritem{jb.off, jb.shard_len,
+                                    jb.img_off + uint64_t(b) * jb.img_stride,
+                                    jb.img_stride, j, npat + bad[b]});
+    }
+    if (rp.cls == GFRS_RPAT_FUSED)
+      per[rp.gm].push_back(gfrs_ritem{jb.off, jb.shard_len, jb.img_off,
+                                      jb.img_stride, j, jb.pattern});
+    else
+      out->inplace_jobs.push_back(j);
+  }
+  out->frame_prefix.assign(nitems + out->buckets.size(), 0);
+  for (int gm = 1; gm <= REPAIR_ROWS; gm++) {
+    if (!count[gm]) continue;
+    std::stable_sort(per[gm].begin(), per[gm].end(),
+                     [](const gfrs_ritem &a, const gfrs_ritem &b) {
+                       return a.desc < b.desc;
+                     });
+    const RepairBucket &bk = out->buckets[bucket_of[gm]];
+    for (size_t i = 0; i < per[gm].size(); i++) {
+      out->items.push_back(per[gm][i]);
+      out->frame_prefix[bk.prefix + i + 1] =
+          out->frame_prefix[bk.prefix + i] +
+          (per[gm][i].shard_len - 1) / REPAIR_PAYLOAD + 1;
+    }
+  }
+  return GFRS_OK;
+}
+
 }  // namespace gfrs
 
 /* ---- GPU-free diagnostic export (include/gfrs.h) ---- */
+
+extern "C" int gfrs_compute_repair_queue_schedule(
+    const gfrs_tactic *t, const gfrs_rjob *jobs, int njobs,
+    const int32_t *bad_idx, const int32_t *bad_off, int npat,
+    int64_t block_len, const uint64_t *bids, const uint64_t *vuids,
+    int item_cap, int image_cap, gfrs_ritem *items, uint64_t *frame_prefix,
+    int *nitems, gfrs_rbucket *buckets, int *nbuckets, gfrs_rimage *images,
+    int *nimages, int32_t *pat_class, int32_t *pat_gm, int32_t *pat_nw,
+    uint32_t *pat_colpack, int32_t *inplace_jobs, int *ninplace) {
+  using namespace gfrs;
+  if (!tactic_valid(t) || t->m == 0) return GFRS_ERR_INVALID_CODEMODE;
+  if (njobs <= 0 || npat <= 0) return GFRS_ERR_INVALID_SHARDS;
+  int rc = queue_offsets_check(bad_off, npat);
+  if (rc != GFRS_OK) return rc;
+  Code c;
+  if (!code_build(*t, &c)) return GFRS_ERR_SINGULAR;
+  std::vector<RepairPattern> pats(npat);
+  for (int p = 0; p < npat; p++) {
+    Plan pl;
+    rc = repair_pattern(c, bad_idx + bad_off[p], bad_off[p + 1] - bad_off[p],
+                        &pl, &pats[p]);
+    if (rc != GFRS_OK) return rc;
+  }
+  if (block_len != REPAIR_BLOCK) return GFRS_ERR_UNSUPPORTED;
+  RepairSchedule s;
+  rc = repair_schedule(jobs, njobs, pats.data(), npat, bad_idx, bad_off, 0,
+                       bids, vuids, &s);
+  if (rc != GFRS_OK) return rc;
+  if (s.items.size() > size_t(item_cap < 0 ? 0 : item_cap) ||
+      s.images.size() > size_t(image_cap < 0 ? 0 : image_cap))
+    return GFRS_ERR_NOMEM;
+  *nitems = int(s.items.size());
+  *nbuckets = int(s.buckets.size());
+  *nimages = int(s.images.size());
+  *ninplace = int(s.inplace_jobs.size());
+  std::copy(s.items.begin(), s.items.end(), items);
+  std::copy(s.frame_prefix.begin(), s.frame_prefix.end(), frame_prefix);
+  for (size_t b = 0; b < s.buckets.size(); b++)
+    buckets[b] = gfrs_rbucket{s.buckets[b].gm, int32_t(s.buckets[b].first),
+                              int32_t(s.buckets[b].count), 0};
+  std::copy(s.images.begin(), s.images.end(), images);
+  for (int p = 0; p < npat; p++) {
+    pat_class[p] = pats[p].cls;
+    pat_gm[p] = pats[p].gm;
+    pat_nw[p] = pats[p].nw;
+    pat_colpack[p] = pats[p].colpack;
+  }
+  std::copy(s.inplace_jobs.begin(), s.inplace_jobs.end(), inplace_jobs);
+  return GFRS_OK;
+}
 
 extern "C" int gfrs_compute_queue_schedule(
     const gfrs_tactic *t, const gfrs_qjob *jobs, int njobs,

@@ -164,6 +164,71 @@ int queue_schedule(const gfrs_qjob *jobs, int njobs, const QueuePattern *pats,
 /* bad_off: npat+1 non-decreasing entries starting at 0 */
 int queue_offsets_check(const int32_t *bad_off, int npat);
 
+/* ---- the repair-image queue (gfrs_repair_queue) ----
+ * gfrs_repair_batch as a queue.  A pattern is FUSED when the gate of
+ * gfrs_repair_batch holds for it; it then has a plan_fused_repair plan of
+ * gm = rebuild + check rows <= 4 and runs the fused frame kernel.  Every
+ * other pattern is IN-PLACE: the schedule of gfrs_reconstruct_verify_queue
+ * reconstructs and verifies its jobs in `base`, and each repaired shard is
+ * then framed from `base` by an IDENTITY work item - the fused frame kernel
+ * over the one-input plan {k = 1, coefficient 1, one rebuild row, imap[0] =
+ * the shard} is a pure "frame this shard" kernel - in the 1-row bucket.  So
+ * framing costs at most REPAIR_ROWS launches whatever the tactic is.
+ * Descriptor index of a work item: fused pattern p is p, the identity of
+ * shard s is npat + s. */
+constexpr int REPAIR_ROWS = 4;             /* rows of the fused frame kernel */
+constexpr uint64_t REPAIR_PAYLOAD = 65532; /* raw bytes per image frame */
+constexpr int64_t REPAIR_BLOCK = 65536;    /* the only block_len served */
+
+struct RepairPattern {
+  int cls = GFRS_RPAT_INPLACE;
+  int nbad = 0;
+  int gm = 0, nw = 0;   /* fused: rows of the plan / of them rebuild rows */
+  uint32_t colpack = 0; /* fused: repair_colpack of the caller's order */
+};
+
+/* Validate one pattern (the codes of queue_pattern_check, and
+ * GFRS_ERR_INVALID_SHARDS when it is empty or repeats an index) and class
+ * it; nw and colpack are set, gm is the plan's to tell (repair_pattern, or
+ * the cached plan's row count). */
+int repair_pattern_check(const Code &c, const int32_t *bad, int nbad,
+                         RepairPattern *r);
+/* ... and build the plan_fused_repair plan of a fused pattern (*p stays
+ * empty for an in-place one). */
+int repair_pattern(const Code &c, const int32_t *bad, int nbad, Plan *p,
+                   RepairPattern *r);
+
+/* raw size -> bytes of the on-disk image (header + framed body + footer) */
+uint64_t repair_image_size(uint64_t shard_len);
+
+struct RepairBucket {
+  int gm = 0;
+  size_t first = 0, count = 0; /* items[first, first+count) */
+  size_t prefix = 0; /* its count+1 frame prefix sums start here
+                        (= first + bucket index) */
+};
+
+struct RepairSchedule {
+  std::vector<gfrs_ritem> items;      /* every bucket's items, back to back;
+                                         inside a bucket ordered by
+                                         descriptor, then by caller index */
+  std::vector<uint64_t> frame_prefix; /* exclusive prefix sums of
+                                         ceil(shard_len / REPAIR_PAYLOAD) */
+  std::vector<RepairBucket> buckets;  /* ascending gm, at most REPAIR_ROWS */
+  std::vector<gfrs_rimage> images;    /* id order */
+  std::vector<int32_t> inplace_jobs;  /* caller order */
+};
+
+/* Job validation (gfrs.h, repair-queue contract; dst_addr = the address of
+ * disk_dst, for the alignment rule) and the schedule.  pats carry cls, nbad
+ * and, for fused patterns, gm; bad_idx / bad_off as given by the caller;
+ * bids / vuids may be null. */
+int repair_schedule(const gfrs_rjob *jobs, int njobs,
+                    const RepairPattern *pats, int npat,
+                    const int32_t *bad_idx, const int32_t *bad_off,
+                    uint64_t dst_addr, const uint64_t *bids,
+                    const uint64_t *vuids, RepairSchedule *out);
+
 }  // namespace gfrs
 
 #endif

@@ -327,6 +327,43 @@ class Encoder:
         bits = np.unpackbits(bmn.view(np.uint8), bitorder="little")[:ns]
         return bits.astype(bool).tolist()
 
+    def repair_queue(self, batch, jobs, patterns, disk_dst, bids, vuids,
+                     block_len=65536):
+        """Repair-image queue: repair_batch per job in one call
+        (worker_slice_recover.go:804-888, the loop over bids, with the disk
+        images of datafile.go:342).  batch: flat uint8 device tensor holding
+        every job; jobs: [(off, shard_len, pattern, img_off, img_stride)],
+        shard i of a job at byte off + i*shard_len of batch, the image of
+        the pattern's b-th bad shard at byte img_off + b*img_stride of
+        disk_dst (flat uint8 device tensor); patterns: [[bad shard
+        indices]], none empty; bids/vuids: one per image, job-major, in the
+        pattern's own order.  Returns the per-job verify-fail list, in the
+        caller's job order."""
+        assert batch.is_cuda and batch.is_contiguous()
+        assert disk_dst.is_cuda and disk_dst.is_contiguous()
+        nj = len(jobs)
+        rj = (runtime.RJob * max(1, nj))()
+        for j, (off, ln, pat, img_off, img_stride) in enumerate(jobs):
+            rj[j] = runtime.RJob(off, ln, img_off, img_stride, pat, 0)
+        flat = [i for p in patterns for i in p]
+        offs = [0]
+        for p in patterns:
+            offs.append(offs[-1] + len(p))
+        bad = (ctypes.c_int32 * max(1, len(flat)))(*flat)
+        boff = (ctypes.c_int32 * len(offs))(*offs)
+        abn = np.ascontiguousarray(bids, dtype=np.uint64)
+        avn = np.ascontiguousarray(vuids, dtype=np.uint64)
+        ab = abn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        av = avn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        bm = (ctypes.c_uint64 * max(1, (nj + 63) // 64))()
+        check(lib().gfrs_repair_queue(self._ctx, batch.data_ptr(), rj, nj,
+                                      bad, boff, len(patterns),
+                                      disk_dst.data_ptr(), block_len, ab, av,
+                                      bm), "repair_queue")
+        bmn = np.ctypeslib.as_array(bm)
+        bits = np.unpackbits(bmn.view(np.uint8), bitorder="little")[:nj]
+        return bits.astype(bool).tolist()
+
     def synchronize(self):
         check(lib().gfrs_synchronize(self._ctx), "synchronize")
 

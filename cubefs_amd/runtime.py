@@ -84,6 +84,50 @@ class QBucket(ctypes.Structure):
     ]
 
 
+class RJob(ctypes.Structure):
+    """gfrs_rjob: one job of a repair-image queue."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("img_off", ctypes.c_uint64),
+        ("img_stride", ctypes.c_uint64),
+        ("pattern", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class RItem(ctypes.Structure):
+    """gfrs_ritem: one work item of a repair-image schedule."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("img", ctypes.c_uint64),
+        ("img_stride", ctypes.c_uint64),
+        ("job", ctypes.c_int32),
+        ("desc", ctypes.c_int32),
+    ]
+
+
+class RBucket(ctypes.Structure):
+    """gfrs_rbucket: one frame launch of a repair-image schedule."""
+    _fields_ = [
+        ("gm", ctypes.c_int32),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class RImage(ctypes.Structure):
+    """gfrs_rimage: one entry of a repair-image schedule's image table."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("size", ctypes.c_uint64),
+        ("bid", ctypes.c_uint64),
+        ("vuid", ctypes.c_uint64),
+    ]
+
+
 _lib = None
 
 
@@ -193,6 +237,15 @@ def lib():
             i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
             ctypes.POINTER(QItem), u64p, ip, ctypes.POINTER(QBucket), ip,
             i32p, u8p, i32p, ip]
+        L.gfrs_repair_queue.argtypes = [vp, vp, ctypes.POINTER(RJob),
+                                        ctypes.c_int, i32p, i32p,
+                                        ctypes.c_int, vp, i64, u64p, u64p,
+                                        u64p]
+        L.gfrs_compute_repair_queue_schedule.argtypes = [
+            ctypes.POINTER(Tactic), ctypes.POINTER(RJob), ctypes.c_int, i32p,
+            i32p, ctypes.c_int, i64, u64p, u64p, ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(RItem), u64p, ip, ctypes.POINTER(RBucket), ip,
+            ctypes.POINTER(RImage), ip, i32p, i32p, i32p, u32p, i32p, ip]
         _lib = L
     return _lib
 

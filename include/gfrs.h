@@ -357,6 +357,85 @@ int gfrs_repair_batch(gfrs_ctx *ctx, void *base, size_t shard_len,
                       const uint64_t *bids, const uint64_t *vuids,
                       uint64_t *fail_bitmap);
 
+/* ---- repair-image queue (worker_slice_recover.go:804-888 +
+ * datafile.go:342-407: the loop over bids, with the disk images) ----
+ * gfrs_repair_batch as a queue: every job has its own place, shard length
+ * and erasure pattern (as in gfrs_reconstruct_verify_queue) and gets back a
+ * verdict bit and one pwrite()-able disk image per bad shard of its pattern.
+ * Patterns are given as for gfrs_reconstruct_verify_queue (bad_idx / bad_off,
+ * npat + 1 offsets); jobs, bad_idx, bad_off, bids, vuids and fail_bitmap are
+ * host memory, base and disk_dst device pointers.
+ *
+ * Repair-queue contract (pinned by tests/test_gpu_repair_queue.py):
+ *  - Per-job result.  For each job j the images and bit j of fail_bitmap are
+ *    exactly what gfrs_repair_batch(ctx, base + off, shard_len, <any stride>,
+ *    1, pattern..., disk_dst + img_off, img_stride, ...) produces for that
+ *    stripe alone: images byte-identical to the reference's shard write of
+ *    its reconstruction, in the caller's column order within the pattern
+ *    (the image of the pattern's b-th bad shard at img_off + b*img_stride);
+ *    the verdict is the reference's Reconstruct followed by Verify, local
+ *    stripes included.  A failed job's images are still written, their
+ *    content unspecified, as for gfrs_repair_batch.
+ *  - Ids.  bids and vuids hold one entry per image, job-major, in the
+ *    pattern's own order: job j's first id sits at the sum of the pattern
+ *    sizes of jobs 0..j-1.
+ *  - Bit numbering.  Bit j refers to the caller's job order; fail_bitmap
+ *    holds (njobs+63)/64 words.
+ *  - Layout.  Sources need no alignment.  disk_dst + img_off and img_stride
+ *    are multiples of 4.  In disk_dst only the declared images are written:
+ *    nothing between images, nothing past an image's gfrs_shard_disk_size
+ *    bytes.  In base, surviving shards and the gaps between jobs are never
+ *    written; the bad shards' regions of base are unspecified after the
+ *    call, as for gfrs_repair_batch.  Overlapping jobs or images are a
+ *    caller error (not checked).
+ *  - Validation.  Everything is validated before the first launch, and any
+ *    error returns its code and writes nothing, neither in base nor in
+ *    disk_dst:
+ *      every pattern, used by a job or not, with the codes of
+ *      gfrs_reconstruct_verify_queue (GFRS_ERR_INVALID_SHARDS for an index
+ *      out of range, GFRS_ERR_TOO_FEW_SHARDS for more than m global losses);
+ *      GFRS_ERR_INVALID_SHARDS for a pattern that is empty or repeats an
+ *      index - this call is strict for every tactic, where the RS(6+6)
+ *      legacy path of gfrs_repair_batch tolerates a repeat;
+ *      GFRS_ERR_INVALID_SHARDS for njobs <= 0, npat <= 0, a malformed
+ *      bad_off, pattern outside [0, npat), reserved != 0, a misaligned
+ *      img_off or img_stride, or img_stride below the image size;
+ *      GFRS_ERR_SHARD_NO_DATA for shard_len == 0;
+ *      GFRS_ERR_UNSUPPORTED for block_len != 65536 (the only frame size
+ *      blobnode writes; the fused kernels have it as a compile-time
+ *      constant).
+ *  - Blocking.  The call blocks until the bitmap is ready, runs on the
+ *    context stream and takes the context mutex once.
+ *  - Launch bound.  A pattern the fused kernel of gfrs_repair_batch serves
+ *    (m >= 1, m + l <= 4, n + m + l <= 16, at most m global losses) is
+ *    reconstructed, verified and framed in one pass; all such jobs of a queue
+ *    share at most 4 launches (one per row count).  Every other pattern
+ *    (RS(6+6), 17 shards, LRC outside the budget) is reconstructed and
+ *    verified in base by the schedule of gfrs_reconstruct_verify_queue, at
+ *    most 4 * ceil(max_rows / 4) launches, and its repaired shards are then
+ *    framed from base by the same <= 4 launches.  One more launch writes
+ *    every header and footer.  So a queue costs at most
+ *    4 + 4 * ceil(max_rows / 4) + 1 kernel launches whatever njobs and npat
+ *    are - except for jobs of LRC slow patterns (see the queue contract
+ *    above), which are reconstructed and verified one at a time.
+ *  - A job of at most 4096 bytes per shard still occupies one workgroup per
+ *    image frame (small jobs are not packed together). */
+typedef struct gfrs_rjob {
+  uint64_t off;        /* shard i of the job at base + off + i*shard_len */
+  uint64_t shard_len;  /* > 0, any value, no alignment */
+  uint64_t img_off;    /* image of the pattern's b-th bad shard at
+                          disk_dst + img_off + b*img_stride */
+  uint64_t img_stride; /* >= gfrs_shard_disk_size(shard_len, 65536) */
+  int32_t pattern;     /* 0 <= pattern < npat */
+  int32_t reserved;    /* must be 0 */
+} gfrs_rjob;
+
+int gfrs_repair_queue(gfrs_ctx *ctx, void *base, const gfrs_rjob *jobs,
+                      int njobs, const int32_t *bad_idx,
+                      const int32_t *bad_off, int npat, void *disk_dst,
+                      int64_t block_len, const uint64_t *bids,
+                      const uint64_t *vuids, uint64_t *fail_bitmap);
+
 /* ---- ec.Buffer size math (buf.go:67-133) ---- */
 int gfrs_buffer_sizes(const gfrs_tactic *t, int64_t data_size,
                       int64_t *shard_size, int64_t *ec_data_size,
@@ -415,6 +494,49 @@ int gfrs_compute_queue_schedule(const gfrs_tactic *t, const gfrs_qjob *jobs,
                                 int *nbuckets, int32_t *pat_nout,
                                 uint8_t *pat_slow, int32_t *slow_jobs,
                                 int *nslow);
+/* GPU-free: what gfrs_repair_queue would upload for a queue, with the same
+ * builder, so CPU tests can check it without a device.
+ *   Pattern class: GFRS_RPAT_FUSED patterns run the fused frame kernel over
+ *   their plan (pat_gm rows of which pat_nw rebuild, pat_colpack nibble r =
+ *   the caller's image column of rebuild row r); the others are reconstructed
+ *   in base first (GFRS_RPAT_INPLACE_SLOW: one job at a time) and their jobs
+ *   are listed in inplace_jobs, caller order.
+ *   Work items: a fused job is one item of its pattern's descriptor (desc =
+ *   pattern index) in the bucket of pat_gm rows; an in-place job is one
+ *   identity item per bad shard s (desc = npat + s: k = 1, coefficient 1,
+ *   one rebuild row, input s) in the 1-row bucket, img pointing at that
+ *   shard's own image.  At most one bucket per row count, ascending; bucket
+ *   b owns items[first, first+count), ordered by descriptor, then by caller
+ *   index, and the count+1 exclusive prefix sums of ceil(shard_len / 65532)
+ *   at frame_prefix[first + b ...].
+ *   Image table: one entry per image in id order (job-major, the pattern's
+ *   own order): byte offset in disk_dst, raw size, bid, vuid.
+ * items holds item_cap entries, frame_prefix item_cap + 4, buckets 4, images
+ * image_cap, pat_* npat, inplace_jobs njobs (GFRS_ERR_NOMEM when the
+ * schedule is larger).  bids / vuids may be NULL (zeros).  Returns the
+ * validation codes of gfrs_repair_queue, taking disk_dst as 4-aligned. */
+enum { GFRS_RPAT_FUSED = 0, GFRS_RPAT_INPLACE = 1, GFRS_RPAT_INPLACE_SLOW = 2 };
+typedef struct gfrs_ritem {
+  uint64_t off, shard_len; /* of the job */
+  uint64_t img;            /* byte offset in disk_dst of image column 0 */
+  uint64_t img_stride;     /* between the item's image columns */
+  int32_t job;             /* caller's index */
+  int32_t desc;            /* descriptor index */
+} gfrs_ritem;
+typedef struct gfrs_rbucket {
+  int32_t gm, first, count, reserved;
+} gfrs_rbucket;
+typedef struct gfrs_rimage {
+  uint64_t off, size, bid, vuid;
+} gfrs_rimage;
+int gfrs_compute_repair_queue_schedule(
+    const gfrs_tactic *t, const gfrs_rjob *jobs, int njobs,
+    const int32_t *bad_idx, const int32_t *bad_off, int npat,
+    int64_t block_len, const uint64_t *bids, const uint64_t *vuids,
+    int item_cap, int image_cap, gfrs_ritem *items, uint64_t *frame_prefix,
+    int *nitems, gfrs_rbucket *buckets, int *nbuckets, gfrs_rimage *images,
+    int *nimages, int32_t *pat_class, int32_t *pat_gm, int32_t *pat_nw,
+    uint32_t *pat_colpack, int32_t *inplace_jobs, int *ninplace);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);

@@ -9,7 +9,17 @@ had before it, RS(12+4), wall time of the blocking calls.
  (c) small    65536 jobs x 2 KiB, one pattern: the queue vs the same loop
      (what the missing small-job packing costs).
 
-(a) runs on random data with encoded parity; (b) and (c) on a zeroed buffer
+and gfrs_repair_queue (the same with the disk images) against
+gfrs_repair_batch:
+
+ (d) uniform  512 jobs x 4 MiB, one pattern [1]: the queue vs ONE
+     gfrs_repair_batch over the same buffers, three interleaved medians of
+     each - the batch call (an unchanged kernel) is the yardstick and its
+     own spread between medians the noise floor.
+ (e) mixed    the 4096-job queue of (b), [6] in place of the verify-only
+     pattern: the queue vs a loop of single-job gfrs_repair_batch calls.
+
+(a) and (d) run on random data with encoded parity; the others on a zeroed buffer
 (a valid stripe: zero parity), since the kernels' work does not depend on
 the data.  One JSON line on stdout; --out also writes it to a file.
 """
@@ -28,6 +38,8 @@ from cubefs_amd import codemode, ec, runtime  # noqa: E402
 
 KIB, MIB = 1 << 10, 1 << 20
 PATTERNS = [[1], [], [0, 13], [2, 5, 11, 15], [12], [3, 7], [4, 14, 15], [9]]
+# a repair has something to write: [6] stands in for the verify-only pattern
+REPAIR_PATTERNS = [p or [6] for p in PATTERNS]
 
 
 def timed(fn, reps):
@@ -149,12 +161,117 @@ class Probe:
         return res
 
 
+    # ---- gfrs_repair_queue (d, e): the same, with the disk images ----
+
+    def image_layout(self, jobs, patterns):
+        """Images back to back at the tight 4-aligned stride, job-major."""
+        rjobs, at = [], 0
+        for off, ln, pat in jobs:
+            stride = (self.L.gfrs_shard_disk_size(ln, 65536) + 3) // 4 * 4
+            rjobs.append((off, ln, pat, at, stride))
+            at += stride * len(patterns[pat])
+        return rjobs, at
+
+    def rargs(self, rjobs, patterns):
+        rj = (runtime.RJob * len(rjobs))()
+        for j, (off, ln, pat, img_off, stride) in enumerate(rjobs):
+            rj[j] = runtime.RJob(off, ln, img_off, stride, pat, 0)
+        flat = [i for p in patterns for i in p]
+        offs = [0]
+        for p in patterns:
+            offs.append(offs[-1] + len(p))
+        nimg = sum(len(patterns[job[2]]) for job in rjobs)
+        self.bads = [((ctypes.c_int32 * len(p))(*p), len(p))
+                     for p in patterns]
+        self.ids = ((ctypes.c_uint64 * nimg)(*range(1, nimg + 1)),
+                    (ctypes.c_uint64 * nimg)(*range(7, nimg + 7)))
+        return (rj, len(rjobs), (ctypes.c_int32 * len(flat))(*flat),
+                (ctypes.c_int32 * len(offs))(*offs), len(patterns))
+
+    def rqueue(self, buf, dst, rargs, njobs):
+        bm = (ctypes.c_uint64 * ((njobs + 63) // 64))()
+        rc = self.L.gfrs_repair_queue(self.enc._ctx, buf.data_ptr(), *rargs,
+                                      dst.data_ptr(), 65536, self.ids[0],
+                                      self.ids[1], bm)
+        assert rc == 0 and not any(bm), rc
+
+    def rloop(self, buf, dst, rjobs):
+        bm = (ctypes.c_uint64 * 1)()
+        base, out = buf.data_ptr(), dst.data_ptr()
+        call = self.L.gfrs_repair_batch
+        ctx = self.enc._ctx
+        for off, ln, pat, img_off, stride in rjobs:
+            bad, nbad = self.bads[pat]
+            rc = call(ctx, base + off, ln, self.total * ln, 1, bad, nbad,
+                      out + img_off, stride, 65536, self.ids[0], self.ids[1],
+                      bm)
+            assert rc == 0 and bm[0] == 0, (rc, bm[0])
+
+    def repair_uniform(self, njobs, slen, reps):
+        """(d): the queue vs ONE gfrs_repair_batch over the same buffers;
+        three medians of each, interleaved, so that the batch call's own
+        run-to-run spread is on record next to the difference."""
+        jobs, nbytes = self.layout([slen] * njobs, 1)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        for lo in range(0, nbytes, 1 << 30):
+            part = buf[lo:lo + (1 << 30)]
+            part.copy_(torch.randint(0, 256, (part.numel(),),
+                                     dtype=torch.uint8, device="cuda"))
+        stride = self.total * slen
+        rc = self.L.gfrs_encode_batch(self.enc._ctx, buf.data_ptr(), slen,
+                                      stride, njobs)
+        assert rc == 0, rc
+        self.enc.synchronize()
+        rjobs, nimg_bytes = self.image_layout(jobs, PATTERNS[:1])
+        dst = torch.empty(nimg_bytes, dtype=torch.uint8, device="cuda")
+        rargs = self.rargs(rjobs, PATTERNS[:1])
+        bad, nbad = self.bads[0]
+        bm = (ctypes.c_uint64 * ((njobs + 63) // 64))()
+
+        def batch():
+            rc = self.L.gfrs_repair_batch(
+                self.enc._ctx, buf.data_ptr(), slen, stride, njobs, bad,
+                nbad, dst.data_ptr(), rjobs[0][4], 65536, self.ids[0],
+                self.ids[1], bm)
+            assert rc == 0 and not any(bm), rc
+
+        res = {"njobs": njobs, "shard_len": slen}
+        for i in (1, 2, 3):
+            res["batch_%d" % i] = timed(batch, reps)
+            res["queue_%d" % i] = timed(
+                lambda: self.rqueue(buf, dst, rargs, njobs), reps)
+        bs = [res["batch_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        qs = [res["queue_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        res["batch_medians_ms"], res["queue_medians_ms"] = bs, qs
+        res["batch_spread"] = round(max(bs) / min(bs) - 1, 4)
+        res["queue_over_batch"] = round(statistics.median(qs) /
+                                        statistics.median(bs), 4)
+        res["moved_GB"] = round(njobs * slen * (self.t.N + self.t.M) / 1e9, 3)
+        return res
+
+    def repair_versus_loop(self, lens, patterns, reps, loop_reps):
+        """(e): the queue vs a loop of single-job gfrs_repair_batch calls."""
+        jobs, nbytes = self.layout(lens, len(patterns))
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        rjobs, nimg_bytes = self.image_layout(jobs, patterns)
+        dst = torch.empty(nimg_bytes, dtype=torch.uint8, device="cuda")
+        rargs = self.rargs(rjobs, patterns)
+        res = {"njobs": len(jobs), "bytes": nbytes, "image_bytes": nimg_bytes,
+               "npat": len(patterns),
+               "queue": timed(
+                   lambda: self.rqueue(buf, dst, rargs, len(jobs)), reps),
+               "loop": timed(lambda: self.rloop(buf, dst, rjobs), loop_reps)}
+        res["loop_over_queue"] = round(res["loop"]["median_ms"] /
+                                       res["queue"]["median_ms"], 2)
+        return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--scale", type=int, default=1,
                     help="divide every job count by this (dry runs)")
-    ap.add_argument("--only", default="abc",
+    ap.add_argument("--only", default="abcde",
                     help="which configurations to run, e.g. 'ac'")
     a = ap.parse_args()
     p = Probe()
@@ -175,6 +292,17 @@ def main():
     if "c" in a.only:
         out["c_small"] = p.versus_loop([2 * KIB] * (65536 // a.scale), 1,
                                        reps=5, loop_reps=2)
+        torch.cuda.empty_cache()
+    if "d" in a.only:
+        out["d_repair_uniform"] = p.repair_uniform(512 // a.scale, 4 * MIB,
+                                                   reps=7)
+        torch.cuda.empty_cache()
+    if "e" in a.only:
+        rng = random.Random(7)               # the lengths and patterns of (b)
+        lens = [rng.choice([64 * KIB, MIB, 4 * MIB])
+                for _ in range(4096 // a.scale)]
+        out["e_repair_mixed"] = p.repair_versus_loop(lens, REPAIR_PATTERNS,
+                                                     reps=5, loop_reps=3)
     line = json.dumps(out)
     print(line)
     if a.out:
