@@ -233,6 +233,9 @@ struct gfrs_ctx_impl {
                        prefix sums of one call */
   DevBuf repair_buf; /* repair-image queue: descriptors, work items, frame
                         prefix sums, image table of one call */
+  DevBuf encq_buf; /* encode+frame queue: work items, frame prefix sums of
+                      one call */
+  PinBuf encq_pin; /* ... and the pinned host copy it is uploaded from */
 
   /* finalize-pipeline resources (repair path): shard_finalize of chunk i
    * runs on aux_stream behind an event while chunk i+1's repair kernel
@@ -1576,6 +1579,83 @@ int gfrs_repair_queue(gfrs_ctx *ctx, void *base, const gfrs_rjob *jobs,
     return rc != GFRS_OK ? rc : hip_fail("repair_queue launch", e);
   }
   return fail_finish(&c->fail_buf, njobs, c->stream, fail_bitmap);
+}
+
+/* The encode+frame queue: gfrs_encode_frame_batch per job, as one call.
+ * gfrs_plan.cpp validates the jobs and sorts them into at most 6 buckets;
+ * this function uploads one blob [work items | frame prefix sums], issues the
+ * small buckets, then the frame buckets, and syncs once.  Tactics outside the
+ * gate of the fused kernels run their jobs one at a time as the composition
+ * the batch call falls back to. */
+int gfrs_encode_frame_queue(gfrs_ctx *ctx, void *framed, void *base,
+                            const gfrs_ejob *jobs, int njobs,
+                            int64_t block_len) {
+  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+  const Code &cd = c->code;
+  const gfrs_tactic &t = cd.t;
+  int rc = encode_queue_block_check(block_len);
+  if (rc != GFRS_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+  EncSchedule sched;
+  rc = encode_queue_schedule(jobs, njobs, (uint64_t)framed, &sched);
+  if (rc != GFRS_OK) return rc;
+  const bool fused =
+      encode_frame_fused(cd) && (t.l == 0 || c->fused_lrc_ok);
+  hipError_t e = hipSuccess;
+  if (fused) {
+    /* the blob goes through pinned memory (a 65536-job queue uploads 2.6 MB);
+     * the buffer is the context's, reused under its mutex, and the call
+     * syncs before it returns */
+    const size_t o_prefix = sched.items.size() * sizeof(gfrs_eitem);
+    const size_t nbytes = o_prefix + sched.frame_prefix.size() * 8;
+    if ((rc = c->encq_buf.ensure(nbytes)) != GFRS_OK) return rc;
+    if ((rc = c->encq_pin.ensure(nbytes)) != GFRS_OK) return rc;
+    uint8_t *blob = (uint8_t *)c->encq_pin.p;
+    memcpy(blob, sched.items.data(), o_prefix);
+    if (nbytes > o_prefix)
+      memcpy(blob + o_prefix, sched.frame_prefix.data(), nbytes - o_prefix);
+    e = hipMemcpyAsync(c->encq_buf.p, blob, nbytes, hipMemcpyHostToDevice,
+                       c->stream);
+    if (e == hipSuccess) {
+      const uint8_t *dq = (const uint8_t *)c->encq_buf.p;
+      const DevPlan &pl = t.l == 0 ? c->enc_plan : c->fused_lrc;
+      const int gm = t.m + t.l;
+      for (const EncBucket &b : sched.buckets) {
+        const gfrs_eitem *items = (const gfrs_eitem *)dq + b.first;
+        if (b.kind == GFRS_EQ_SMALL)
+          launch_rs_encode_frame_small_queue((uint8_t *)framed,
+                                             (uint64_t)base, items,
+                                             uint32_t(b.count), t.n, gm,
+                                             b.param, pl.tab(), c->stream);
+        else
+          launch_rs_encode_frame_queue(
+              (uint8_t *)framed, (uint64_t)base, items,
+              (const uint64_t *)(dq + o_prefix) + b.prefix, uint32_t(b.count),
+              sched.frame_prefix[b.prefix + b.count], t.n, gm, pl.tab(),
+              b.param, c->stream);
+      }
+      e = hipGetLastError();
+    }
+  } else {
+    for (int j = 0; j < njobs && rc == GFRS_OK; j++) {
+      const gfrs_ejob &jb = jobs[j];
+      uint8_t *src = (uint8_t *)base + jb.off;
+      rc = encode_batch_impl(c, src, jb.shard_len,
+                             size_t(cd.total) * jb.shard_len, 1, c->stream);
+      if (rc == GFRS_OK)
+        rc = crc32b_encode_batch_impl(c, (uint8_t *)framed + jb.img_off,
+                                      jb.img_stride, src, jb.shard_len,
+                                      int64_t(jb.shard_len), block_len,
+                                      cd.total);
+    }
+  }
+  hipError_t se = hipStreamSynchronize(c->stream); /* the one sync; the blob
+                                                      is read until here */
+  if (rc != GFRS_OK) return rc;
+  if (e != hipSuccess) return hip_fail("encode_frame_queue launch", e);
+  if (se != hipSuccess) return hip_fail("encode_frame_queue sync", se);
+  return GFRS_OK;
 }
 
 int gfrs_update_idx(gfrs_ctx *ctx, const void *old_shard,

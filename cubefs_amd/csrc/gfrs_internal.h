@@ -80,6 +80,26 @@ void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
                             int m, const uint8_t *tabs, int nstripes,
                             hipStream_t s);
 
+/* Encode+frame queue: one bucket of the encode schedule (gfrs_plan.h).  An
+ * item is launch_rs_encode_frame over its own job:
+ *   data shard c at base + item.off + c * item.shard_len,
+ *   image of shard j at dst + item.img + j * item.img_stride.
+ * Frame buckets: frame_prefix holds the nitems+1 exclusive prefix sums of
+ * ceil(shard_len / 65532), total_frames its last entry; var is the batch
+ * launcher's variant (76: 3 waves, plain stores; 87: 4 waves, nontemporal).
+ * Small buckets: every item has ceil(shard_len / 1024) == ni, and item i is
+ * wave i.  tabs: the context's encode plan, [m*k][32]. */
+void launch_rs_encode_frame_queue(uint8_t *dst, uint64_t base,
+                                  const gfrs_eitem *items,
+                                  const uint64_t *frame_prefix,
+                                  uint32_t nitems, uint64_t total_frames,
+                                  int k, int m, const uint8_t *tabs, int var,
+                                  hipStream_t s);
+void launch_rs_encode_frame_small_queue(uint8_t *dst, uint64_t base,
+                                        const gfrs_eitem *items,
+                                        uint32_t nitems, int k, int m, int ni,
+                                        const uint8_t *tabs, hipStream_t s);
+
 /* sized coder (crc32block/sized_coder.go): payload ‖ CRC32(BE) frames,
  * 512-B tail alignment handled by the host. */
 void launch_sized_encode(uint8_t *dst, size_t dst_stride, const uint8_t *src,

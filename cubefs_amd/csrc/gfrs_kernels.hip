@@ -3911,6 +3911,522 @@ void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
 #undef GFRS_EF_GO
 }
 
+/* Encode+frame queue, frame class: rs_encode_frame_reg_k<GM, WPS, 0, 0, 1,
+ * ST> over the work items of one frame bucket of the encode schedule
+ * (gfrs_plan.h).  The math of a frame - the 16 KiB passes, the register CRC
+ * with the chained per-pass operators, the one-unit lookahead, the
+ * LDS-staged tail bytes, the frame header store - is the batch kernel's;
+ * what differs is where a frame comes from, which is rs_repair_frame_queue_k's
+ * way:
+ *  - the grid is capped and block b walks frames b, b + grid, b + 2*grid, ...
+ *    of the bucket: the batch kernel's grid-stride walk, which keeps
+ *    co-resident blocks on neighbouring frames.  (rs_repair_frame_queue_k's
+ *    CONTIGUOUS ranges [b*per_blk, (b+1)*per_blk) measured 23 % slower here
+ *    on the headline shape)  frame -> work item:
+ *    one binary search over the frame prefix sums at the block's first
+ *    frame, then a forward gallop + bisection from the current item (one
+ *    compare while the frame stays inside it).  All of it depends on
+ *    blockIdx and kernel arguments only, so the search and the item are
+ *    scalar loads;
+ *  - there is one encode plan per context: ctab is staged once, before the
+ *    loop, and never restaged;
+ *  - every pointer is rebuilt from base + item.off; the image row of shard j
+ *    is dst + item.img + j*item.img_stride + f*65536;
+ *  - cross-frame prefetch: the batch kernel computes the next frame's unit 0
+ *    from the CURRENT shard_len and stripe arithmetic.  Here the next frame
+ *    may belong to another job, so after a frame's last pass the address,
+ *    length and mask come from the NEXT item's own off and shard_len; `pref`
+ *    (block-uniform) says that vnext holds exactly the loads the top of the
+ *    next frame would issue, otherwise the top issues them.  No load ever
+ *    leaves the data shards of the job it belongs to;
+ *  - no tiny-last-frame fold: a trailing frame of <= 64 payload bytes is a
+ *    frame of the prefix sums like any other and gets its own workgroup
+ *    iteration. */
+template <int GM, int WPS, int ST>
+__global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_queue_k(
+    uint8_t *__restrict__ dst /* framed */, uint64_t base,
+    const gfrs_eitem *__restrict__ items,
+    const uint64_t *__restrict__ frame_prefix, uint32_t nitems,
+    uint64_t total_frames, int k,
+    const uint8_t *__restrict__ tabs /* [GM*k][32] */) {
+  constexpr int EF_PASS = 16384;
+  constexpr int EF_PASSES = 4;
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+
+  /* block b walks frames b, b + grid, b + 2*grid, ... */
+  const uint64_t f_step = uint64_t(gridDim.x);
+  const uint64_t f_lo = uint64_t(blockIdx.x);
+  const uint64_t f_hi = total_frames;
+  if (f_lo >= f_hi) return; /* whole block, before any barrier */
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t(*tab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem);
+  uint32_t(*stab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem + 8192);
+  uint32_t *red = reinterpret_cast<uint32_t *>(smem + 12288);
+  uint32_t *x8tab = reinterpret_cast<uint32_t *>(smem + 12288 + EF_RED);
+  uint8_t *tailb = smem + 12288 + EF_RED + 64;
+  uint8_t *ctab = smem + 12288 + EF_RED + 64 + 256;
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift4k[0][0])[i];
+  for (int i = threadIdx.x; i < GM * k * 2; i += CRC_BLOCKT)
+    reinterpret_cast<uint4 *>(ctab)[i] =
+        reinterpret_cast<const uint4 *>(tabs)[i];
+  if (threadIdx.x == 0) {
+    uint32_t v = 0x80000000u;
+    for (int j = 0; j < 16; j++) {
+      x8tab[j] = v;
+      v = gf2_mulmod_d(v, g_pow8[0]);
+    }
+  }
+  const int64_t lane16 = int64_t(threadIdx.x) * 16;
+  const int lane16i = int(threadIdx.x) * 16;
+  constexpr uint32_t INV16K = 0x479933FCu;
+  const uint32_t op_pA =
+      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16 + 16)));
+  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
+  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
+  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  const uint32_t it_full =
+      gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
+  __syncthreads();
+
+  /* largest it with frame_prefix[it] <= f_lo (frame_prefix[0] == 0) */
+  uint32_t it = 0;
+  for (uint32_t hi = nitems; hi - it > 1;) {
+    const uint32_t mid = it + (hi - it) / 2;
+    if (frame_prefix[mid] <= f_lo)
+      it = mid;
+    else
+      hi = mid;
+  }
+
+  uint4 vnext[4] = {uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0},
+                    uint4{0, 0, 0, 0}};
+  bool pref = false; /* vnext = pass 0, unit 0 of the frame about to start */
+
+  /* `it` -> the item of frame `to` (>= the frame `it` stands for): gallop,
+   * then bisect; one compare when the frame belongs to the same item */
+  auto advance = [&](uint32_t from, uint64_t to) {
+    if (frame_prefix[from + 1] > to) return from; /* from + 1 <= nitems */
+    uint32_t lo = from + 1, step = 1;
+    while (lo + step < nitems && frame_prefix[lo + step] <= to) {
+      lo += step;
+      step <<= 1;
+    }
+    uint32_t hi = lo + step < nitems ? lo + step : nitems;
+    while (hi - lo > 1) { /* frame_prefix[lo] <= to < frame_prefix[hi] */
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (frame_prefix[mid] <= to)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    return lo;
+  };
+
+  for (uint64_t fr = f_lo; fr < f_hi; fr += f_step) {
+    it = advance(it, fr); /* a no-op after a prefetch */
+    const gfrs_eitem item = items[it];
+    const size_t shard_len = item.shard_len;
+    const int64_t f = int64_t(fr - frame_prefix[it]);
+    const int64_t p0 = f * payload_full;
+    const int64_t payload = i64min(payload_full, int64_t(shard_len) - p0);
+    const uint8_t *sbase = as_global(base + item.off);
+    /* frame f of the image of shard 0; shard j at + j * img_stride */
+    uint8_t *irow = dst + item.img + f * block_len;
+
+    uint4 acc[GM][4];
+    if (!pref) { /* pass 0, unit 0 */
+      const int rb0 = int(i64min(int64_t(EF_PASS), payload));
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        vnext[i] = off + 16 <= rb0
+                       ? *reinterpret_cast<const uint4 *>(sbase + p0 + off)
+                       : uint4{0, 0, 0, 0};
+      }
+    }
+    pref = false;
+    for (int j = threadIdx.x; j < 64; j += CRC_BLOCKT) red[j] = 0;
+    __syncthreads();
+
+    for (int h = 0; h < EF_PASSES; h++) {
+      const int64_t r0 = int64_t(h) * EF_PASS;
+      const int64_t rbytes = i64min(int64_t(EF_PASS), payload - r0);
+      if (rbytes <= 0) break;
+#pragma unroll
+      for (int r = 0; r < GM; r++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[r][i] = uint4{0, 0, 0, 0};
+
+      uint32_t op = h == 0   ? op_pA
+                    : h == 1 ? op_pB
+                    : h == 2 ? op_pC
+                             : op_pD;
+      if (h == EF_PASSES - 1 && threadIdx.x == 255)
+        op = shift4k(op, stab); /* lane 255's last pass has 3 pieces */
+      if (payload != payload_full) {
+        int np = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (int64_t(i) * 4096 + lane16 + 16 <= rbytes) np = i + 1;
+        const int64_t end =
+            np ? r0 + int64_t(np - 1) * 4096 + lane16 + 16 : r0;
+        op = x8n_d(uint64_t(payload - end));
+      }
+
+      const int rbi = int(rbytes);
+      for (int c = 0; c < k; c++) {
+        const uint8_t *src = sbase + size_t(c) * shard_len + p0 + r0;
+        uint8_t *fdst = irow + size_t(c) * item.img_stride + CRC_LEN + r0;
+        LinTab lt[GM];
+#pragma unroll
+        for (int r = 0; r < GM; r++) lt[r] = lintab_load(ctab, r * k + c);
+        uint4 vcur[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) vcur[i] = vnext[i];
+        if (c + 1 < k) { /* next input's loads fly over this MAC */
+          const uint8_t *nsrc = sbase + size_t(c + 1) * shard_len + p0 + r0;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            vnext[i] = off + 16 <= rbi
+                           ? *reinterpret_cast<const uint4 *>(nsrc + off)
+                           : uint4{0, 0, 0, 0};
+          }
+        }
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int off = i * 4096 + lane16i;
+          if (off + 16 <= rbi) {
+            const uint4 v = vcur[i];
+#pragma unroll
+            for (int d = 0; d < 4; d++)
+              gfmac4_lin_rows<GM>(acc, i, d, (&v.x)[d], lt);
+            fstore16<ST>(fdst + off, v);
+            t = shift4k(t, stab) ^ crc16_reg(v, tab);
+          }
+        }
+        uint32_t part = t ? gf2_mulmod_d(op, t) : 0;
+        if (rbytes < EF_PASS) { /* lane-parallel tail, one byte per lane */
+          const int t0 = (rbi / 16) * 16;
+          const int p = t0 + int(threadIdx.x);
+          if (p < rbi) {
+            const uint8_t x = src[p];
+            fdst[p] = x;
+            tailb[c * 16 + (p - t0)] = x;
+            part ^= gf2_mulmod_d(x8tab[rbi - 1 - p], tab[0][x]);
+          }
+        }
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1)
+          part ^= __shfl_xor(part, sh, 64);
+        if ((threadIdx.x & 63) == 0)
+          red[(threadIdx.x >> 6) * 16 + c] ^= part;
+      }
+      if (rbytes < EF_PASS) __syncthreads(); /* tailb visible to all */
+      { /* unit 0 of the next pass, or of the next frame, flies during the
+           parity rows and the frame epilogue */
+        const int64_t r0n = r0 + EF_PASS;
+        int64_t rbn = i64min(int64_t(EF_PASS), payload - r0n);
+        const uint8_t *nbase = sbase + p0 + r0n;
+        if (rbn <= 0 && fr + f_step < f_hi) {
+          /* this block's next frame, from ITS item (the same job or a later
+           * one: its own off and shard_len); `it` moves on with it - the
+           * rest of this frame works on `item` */
+          it = advance(it, fr + f_step);
+          const gfrs_eitem nx = items[it];
+          const int64_t p0n =
+              int64_t(fr + f_step - frame_prefix[it]) * payload_full;
+          rbn = i64min(int64_t(EF_PASS), int64_t(nx.shard_len) - p0n);
+          nbase = as_global(base + nx.off) + p0n;
+          pref = true;
+        }
+        if (rbn > 0) {
+          const int rbni = int(rbn);
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            vnext[i] = off + 16 <= rbni
+                           ? *reinterpret_cast<const uint4 *>(nbase + off)
+                           : uint4{0, 0, 0, 0};
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < GM; r++) {
+        uint8_t *fdst = irow + size_t(k + r) * item.img_stride + CRC_LEN + r0;
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int off = i * 4096 + lane16i;
+          if (off + 16 <= rbi) {
+            fstore16<ST>(fdst + off, acc[r][i]);
+            t = shift4k(t, stab) ^ crc16_reg(acc[r][i], tab);
+          }
+        }
+        uint32_t part = t ? gf2_mulmod_d(op, t) : 0;
+        if (rbytes < EF_PASS) {
+          const int t0 = (rbi / 16) * 16;
+          const int p = t0 + int(threadIdx.x);
+          if (p < rbi) {
+            uint8_t pv = 0;
+            for (int c2 = 0; c2 < k; c2++) {
+              const uint8_t b = tailb[c2 * 16 + (p - t0)];
+              pv ^= gfmul1_lin(ctab + size_t(r * k + c2) * 32, b);
+            }
+            fdst[p] = pv;
+            part ^= gf2_mulmod_d(x8tab[rbi - 1 - p], tab[0][pv]);
+          }
+        }
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1)
+          part ^= __shfl_xor(part, sh, 64);
+        if ((threadIdx.x & 63) == 0)
+          red[(threadIdx.x >> 6) * 16 + k + r] ^= part;
+      }
+    }
+
+    __syncthreads();
+    { /* one frame-header lane per shard (j < k+GM <= 16, all in wave 0) */
+      const int j = int(threadIdx.x);
+      if (j < k + GM) {
+        const uint32_t itv =
+            payload == payload_full
+                ? it_full
+                : gf2_mulmod_d(x8n_d(uint64_t(payload)), 0xFFFFFFFFu);
+        const uint32_t crc =
+            ~(itv ^ red[j] ^ red[16 + j] ^ red[32 + j] ^ red[48 + j]);
+        *reinterpret_cast<uint32_t *>(irow + size_t(j) * item.img_stride) =
+            crc;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+void launch_rs_encode_frame_queue(uint8_t *dst, uint64_t base,
+                                  const gfrs_eitem *items,
+                                  const uint64_t *frame_prefix,
+                                  uint32_t nitems, uint64_t total_frames,
+                                  int k, int m, const uint8_t *tabs, int var,
+                                  hipStream_t s) {
+  if (nitems == 0 || total_frames == 0) return;
+  /* the cap of fused_grid, read on every launch: GFRS_CRC_GRID forces the
+   * multi-frame walk and the cross-item prefetch at tiny shapes */
+  const uint64_t cap = uint64_t(env_grid("GFRS_CRC_GRID", 16384));
+  int grid = int(total_frames < cap ? total_frames : cap);
+  const int lds = 12288 + EF_RED + 64 + 256 + m * k * 32;
+  /* fused_grid's rule: the stride must not alias the frame position inside
+   * a shard, or whole blocks get only the short last frames.  A bucket has
+   * no single frames-per-shard, so keep the stride coprime with every count
+   * up to 13 (shards below 852 KiB); a forced small grid is left alone */
+  if (uint64_t(grid) < total_frames && grid >= 1024) {
+    auto gcd = [](int a, int b) {
+      while (b) { const int t2 = a % b; a = b; b = t2; }
+      return a;
+    };
+    while (gcd(grid, 2 * 3 * 5 * 7 * 11 * 13) != 1) grid--;
+  }
+#define GFRS_EQ_GO(G, W, S)                                                \
+  hipLaunchKernelGGL((rs_encode_frame_queue_k<G, W, S>), dim3(grid),       \
+                     dim3(CRC_BLOCKT), lds, s, dst, base, items,           \
+                     frame_prefix, nitems, total_frames, k, tabs)
+#define GFRS_EQ_SW(W, S)                                                   \
+  switch (m) {                                                             \
+    case 1: GFRS_EQ_GO(1, W, S); break;                                    \
+    case 2: GFRS_EQ_GO(2, W, S); break;                                    \
+    case 3: GFRS_EQ_GO(3, W, S); break;                                    \
+    default: GFRS_EQ_GO(4, W, S);                                          \
+  }
+  /* the two variants launch_rs_encode_frame picks by shard size: 76 = 3
+   * waves/SIMD, plain stores; 87 = 4 waves/SIMD, nontemporal stores */
+  if (var == 76) { GFRS_EQ_SW(3, 0) } else { GFRS_EQ_SW(4, 1) }
+#undef GFRS_EQ_SW
+#undef GFRS_EQ_GO
+}
+
+/* Encode+frame queue, small class: rs_encode_frame_small_k with the stripe
+ * loop turned into a loop over the items of one small bucket, wave
+ * 4*blockIdx + wv, grid-stride.  Every item of the bucket has
+ * ceil(shard_len / 1024) == NI, so the NI-long loops stay compile-time, but
+ * shard_len itself is per job: what the batch kernel hoists out of its loop
+ * is computed per job here.  A lane's fold operator is x^(8*s), s = the bytes
+ * after its last present piece; s < 1024 and s mod 16 == shard_len mod 16, so
+ * it is one multiply of two LDS table entries, x^(128*(s/16)) and
+ * x^(8*(s%16)), instead of a binary expansion per job; the frame's init term
+ * x^(8*shard_len) * 0xFFFFFFFF likewise (shard_len / 16 <= 256).  The wave
+ * index goes through readfirstlane so the item is a scalar load.  No barrier
+ * after the prologue: a wave with no item left simply leaves the loop. */
+template <int GM, int NI>
+__global__ __launch_bounds__(CRC_BLOCKT, 4) void rs_encode_frame_small_queue_k(
+    uint8_t *__restrict__ dst /* framed */, uint64_t base,
+    const gfrs_eitem *__restrict__ items, uint32_t nitems, int k,
+    const uint8_t *__restrict__ tabs /* [GM*k][32] */) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t(*tab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem);
+  uint32_t(*stab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem + 8192);
+  uint32_t *x8tab = reinterpret_cast<uint32_t *>(smem + 12288);
+  /* x^(8*j) * 0xFFFFFFFF, j < 16 */
+  uint32_t *x8init = reinterpret_cast<uint32_t *>(smem + 12288 + 64);
+  /* x^(128*a), a <= 256 */
+  uint32_t *x128tab = reinterpret_cast<uint32_t *>(smem + 12288 + 128);
+  uint8_t *tailb = smem + 12288 + 128 + 1040; /* per-wave 16x16 tail bytes */
+  uint8_t *ctab = smem + 12288 + 128 + 1040 + 4 * 256;
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift1k[0][0])[i];
+  for (int i = threadIdx.x; i < GM * k * 2; i += CRC_BLOCKT)
+    reinterpret_cast<uint4 *>(ctab)[i] =
+        reinterpret_cast<const uint4 *>(tabs)[i];
+  { /* the operator tables, one entry per lane: no serial thread-0 chain */
+    const uint32_t v = x8n_d(uint64_t(threadIdx.x) * 16);
+    x128tab[threadIdx.x] = v;
+    if (threadIdx.x == 255)
+      x128tab[256] = gf2_mulmod_d(v, g_pow8[4]); /* times x^(8*16) */
+    if (threadIdx.x < 16) {
+      const uint32_t w = x8n_d(uint64_t(threadIdx.x));
+      x8tab[threadIdx.x] = w;
+      x8init[threadIdx.x] = gf2_mulmod_d(w, 0xFFFFFFFFu);
+    }
+  }
+  __syncthreads();
+
+  const int wv = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
+  const int lane = int(threadIdx.x) & 63;
+  const int lane16i = lane * 16;
+  uint8_t *wtail = tailb + wv * 256;
+
+  for (uint32_t w = blockIdx.x * 4 + uint32_t(wv); w < nitems;
+       w += gridDim.x * 4) {
+    const gfrs_eitem item = items[w];
+    const size_t shard_len = item.shard_len;
+    const int pli = int(shard_len); /* <= 4096 */
+    const uint8_t *sbase = as_global(base + item.off);
+    uint8_t *img0 = dst + item.img; /* image of shard j at + j*img_stride */
+    /* lane's fold operator: suffix after its LAST present piece */
+    int np = 0;
+#pragma unroll
+    for (int i = 0; i < NI; i++)
+      if (i * 1024 + lane16i + 16 <= pli) np = i + 1;
+    const int sfx = np ? pli - ((np - 1) * 1024 + lane16i + 16) : 0;
+    const uint32_t op =
+        np ? gf2_mulmod_d(x128tab[sfx >> 4], x8tab[sfx & 15]) : 0;
+    const uint32_t it = gf2_mulmod_d(x128tab[pli >> 4], x8init[pli & 15]);
+    const int t0 = (pli / 16) * 16;
+
+    uint4 acc[GM][NI];
+#pragma unroll
+    for (int r = 0; r < GM; r++)
+#pragma unroll
+      for (int i = 0; i < NI; i++) acc[r][i] = uint4{0, 0, 0, 0};
+
+    for (int c = 0; c < k; c++) {
+      const uint8_t *src = sbase + size_t(c) * shard_len;
+      uint8_t *fdst = img0 + size_t(c) * item.img_stride + CRC_LEN;
+      uint32_t t = 0;
+      LinTab lt[GM];
+#pragma unroll
+      for (int r = 0; r < GM; r++) lt[r] = lintab_load(ctab, r * k + c);
+#pragma unroll
+      for (int i = 0; i < NI; i++) {
+        const int off = i * 1024 + lane16i;
+        if (off + 16 <= pli) {
+          const uint4 v = *reinterpret_cast<const uint4 *>(src + off);
+#pragma unroll
+          for (int d = 0; d < 4; d++)
+            gfmac4_lin_rows_n<GM, NI>(acc, i, d, (&v.x)[d], lt);
+          *reinterpret_cast<uint4 *>(fdst + off) = v;
+          t = shift4k(t, stab) ^ crc16_reg(v, tab); /* stab = x^(8*1024) */
+        }
+      }
+      uint32_t part = t ? gf2_mulmod_d(op, t) : 0;
+      { /* tail bytes, one per lane; stage for the parity tails */
+        const int p = t0 + lane;
+        if (p < pli) {
+          const uint8_t x = src[p];
+          fdst[p] = x;
+          wtail[c * 16 + (p - t0)] = x;
+          part ^= gf2_mulmod_d(x8tab[pli - 1 - p], tab[0][x]);
+        }
+      }
+#pragma unroll
+      for (int sh = 32; sh > 0; sh >>= 1)
+        part ^= __shfl_xor(part, sh, 64);
+      if (lane == 0)
+        *reinterpret_cast<uint32_t *>(img0 + size_t(c) * item.img_stride) =
+            ~(it ^ part);
+    }
+#pragma unroll
+    for (int r = 0; r < GM; r++) {
+      uint8_t *fdst = img0 + size_t(k + r) * item.img_stride + CRC_LEN;
+      uint32_t t = 0;
+#pragma unroll
+      for (int i = 0; i < NI; i++) {
+        const int off = i * 1024 + lane16i;
+        if (off + 16 <= pli) {
+          *reinterpret_cast<uint4 *>(fdst + off) = acc[r][i];
+          t = shift4k(t, stab) ^ crc16_reg(acc[r][i], tab);
+        }
+      }
+      uint32_t part = t ? gf2_mulmod_d(op, t) : 0;
+      {
+        const int p = t0 + lane;
+        if (p < pli) { /* same-wave LDS visibility: no barrier needed */
+          uint8_t pv = 0;
+          for (int c2 = 0; c2 < k; c2++) {
+            const uint8_t b = wtail[c2 * 16 + (p - t0)];
+            pv ^= gfmul1_lin(ctab + size_t(r * k + c2) * 32, b);
+          }
+          fdst[p] = pv;
+          part ^= gf2_mulmod_d(x8tab[pli - 1 - p], tab[0][pv]);
+        }
+      }
+#pragma unroll
+      for (int sh = 32; sh > 0; sh >>= 1)
+        part ^= __shfl_xor(part, sh, 64);
+      if (lane == 0)
+        *reinterpret_cast<uint32_t *>(img0 + size_t(k + r) * item.img_stride) =
+            ~(it ^ part);
+    }
+  }
+}
+
+void launch_rs_encode_frame_small_queue(uint8_t *dst, uint64_t base,
+                                        const gfrs_eitem *items,
+                                        uint32_t nitems, int k, int m, int ni,
+                                        const uint8_t *tabs, hipStream_t s) {
+  if (nitems == 0) return;
+  const int64_t groups = (int64_t(nitems) + 3) / 4;
+  const int64_t cap = env_grid("GFRS_CRC_GRID", 16384);
+  const int grid = int(groups < cap ? groups : cap);
+  const int lds = 12288 + 128 + 1040 + 1024 + m * k * 32;
+#define GFRS_SQ_GO(G, I)                                                  \
+  hipLaunchKernelGGL((rs_encode_frame_small_queue_k<G, I>), dim3(grid),   \
+                     dim3(CRC_BLOCKT), lds, s, dst, base, items, nitems,  \
+                     k, tabs)
+#define GFRS_SQ_NI(G)                                                     \
+  switch (ni) {                                                           \
+    case 1: GFRS_SQ_GO(G, 1); break;                                      \
+    case 2: GFRS_SQ_GO(G, 2); break;                                      \
+    case 3: GFRS_SQ_GO(G, 3); break;                                      \
+    default: GFRS_SQ_GO(G, 4);                                            \
+  }
+  switch (m) {
+    case 1: GFRS_SQ_NI(1); break;
+    case 2: GFRS_SQ_NI(2); break;
+    case 3: GFRS_SQ_NI(3); break;
+    default: GFRS_SQ_NI(4);
+  }
+#undef GFRS_SQ_NI
+#undef GFRS_SQ_GO
+}
+
 /* ------------------------------------------------------------------ */
 /* blobnode on-disk shard codec (core/shard.go:42-111, datafile.go:342)  */
 /* ------------------------------------------------------------------ */

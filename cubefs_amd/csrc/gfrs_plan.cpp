@@ -552,9 +552,105 @@ int repair_schedule(const gfrs_rjob *jobs, int njobs,
   return GFRS_OK;
 }
 
+/* ---- the encode+frame queue ---- */
+
+bool encode_frame_fused(const Code &c) {
+  const gfrs_tactic &t = c.t;
+  return t.m >= 1 && t.m + t.l <= 4 && c.total <= 16 &&
+         (t.l == 0 || lrc_single_pass(c));
+}
+
+uint64_t encode_image_size(uint64_t shard_len) {
+  return shard_len + 4 * ((shard_len - 1) / REPAIR_PAYLOAD + 1);
+}
+
+int encode_queue_block_check(int64_t block_len) {
+  if (block_len <= 0 || block_len % 4096) return GFRS_ERR_INVALID_BLOCK;
+  return block_len == REPAIR_BLOCK ? GFRS_OK : GFRS_ERR_UNSUPPORTED;
+}
+
+int encode_queue_schedule(const gfrs_ejob *jobs, int njobs,
+                          uint64_t framed_addr, EncSchedule *out) {
+  *out = EncSchedule();
+  if (njobs <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
+  /* slots 0..3: small NI 1..4; 4: frame below ENCQ_LARGE_MIN; 5: from it up */
+  auto slot_of = [](uint64_t len) {
+    if (len <= ENCQ_SMALL_MAX) return int((len - 1) / 1024);
+    return len < ENCQ_LARGE_MIN ? 4 : 5;
+  };
+  size_t count[ENCQ_BUCKETS] = {0};
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_ejob &jb = jobs[j];
+    if (jb.reserved != 0) return GFRS_ERR_INVALID_SHARDS;
+    if (jb.shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
+    if ((framed_addr + jb.img_off) % 4 || jb.img_stride % 4 ||
+        jb.img_stride < encode_image_size(jb.shard_len))
+      return GFRS_ERR_INVALID_SHARDS;
+    count[slot_of(jb.shard_len)]++;
+  }
+  size_t fill[ENCQ_BUCKETS], pre[ENCQ_BUCKETS] = {0}, nitems = 0, npre = 0;
+  for (int s = 0; s < ENCQ_BUCKETS; s++) {
+    fill[s] = nitems;
+    if (!count[s]) continue;
+    EncBucket b;
+    b.kind = s < 4 ? GFRS_EQ_SMALL : GFRS_EQ_FRAME;
+    b.param = s < 4 ? s + 1
+                    : (s == 4 ? ENCQ_VAR_SMALL_SHARDS : ENCQ_VAR_LARGE_SHARDS);
+    b.first = nitems;
+    b.count = count[s];
+    if (s >= 4) {
+      b.prefix = pre[s] = npre;
+      npre += count[s] + 1;
+    }
+    nitems += count[s];
+    out->buckets.push_back(b);
+  }
+  out->items.resize(nitems);
+  out->frame_prefix.assign(npre, 0);
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_ejob &jb = jobs[j];
+    const int s = slot_of(jb.shard_len);
+    const size_t at = fill[s]++;
+    out->items[at] =
+        gfrs_eitem{jb.off, jb.shard_len, jb.img_off, jb.img_stride, j, 0};
+    if (s >= 4) {
+      const size_t pi = pre[s]++;
+      out->frame_prefix[pi + 1] =
+          out->frame_prefix[pi] + (jb.shard_len - 1) / REPAIR_PAYLOAD + 1;
+    }
+  }
+  return GFRS_OK;
+}
+
 }  // namespace gfrs
 
 /* ---- GPU-free diagnostic export (include/gfrs.h) ---- */
+
+extern "C" int gfrs_compute_encode_queue_schedule(
+    const gfrs_tactic *t, const gfrs_ejob *jobs, int njobs, int64_t block_len,
+    int item_cap, gfrs_eitem *items, uint64_t *frame_prefix, int *nitems,
+    gfrs_ebucket *buckets, int *nbuckets, int *fused) {
+  using namespace gfrs;
+  if (!tactic_valid(t) || t->m == 0) return GFRS_ERR_INVALID_CODEMODE;
+  int rc = encode_queue_block_check(block_len);
+  if (rc != GFRS_OK) return rc;
+  Code c;
+  if (!code_build(*t, &c)) return GFRS_ERR_SINGULAR;
+  EncSchedule s;
+  if ((rc = encode_queue_schedule(jobs, njobs, 0, &s)) != GFRS_OK) return rc;
+  if (s.items.size() > size_t(item_cap < 0 ? 0 : item_cap))
+    return GFRS_ERR_NOMEM;
+  *nitems = int(s.items.size());
+  *nbuckets = int(s.buckets.size());
+  *fused = encode_frame_fused(c) ? 1 : 0;
+  std::copy(s.items.begin(), s.items.end(), items);
+  std::copy(s.frame_prefix.begin(), s.frame_prefix.end(), frame_prefix);
+  for (size_t b = 0; b < s.buckets.size(); b++)
+    buckets[b] = gfrs_ebucket{s.buckets[b].kind, s.buckets[b].param,
+                              int32_t(s.buckets[b].first),
+                              int32_t(s.buckets[b].count)};
+  return GFRS_OK;
+}
 
 extern "C" int gfrs_compute_repair_queue_schedule(
     const gfrs_tactic *t, const gfrs_rjob *jobs, int njobs,

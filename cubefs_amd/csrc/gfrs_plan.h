@@ -229,6 +229,49 @@ int repair_schedule(const gfrs_rjob *jobs, int njobs,
                     uint64_t dst_addr, const uint64_t *bids,
                     const uint64_t *vuids, RepairSchedule *out);
 
+/* ---- the encode+frame queue (gfrs_encode_frame_queue) ----
+ * gfrs_encode_frame_batch as a queue.  There is one encode plan per context,
+ * so the schedule only decides which kernel form serves which job:
+ *   SMALL  shard_len <= ENCQ_SMALL_MAX: one wave per job, one bucket per
+ *          NI = ceil(shard_len / 1024) = 1..4 (the wave kernel keeps its
+ *          NI-long loops compile-time); item i of the bucket is wave i, so a
+ *          small bucket has no prefix sums;
+ *   FRAME  longer jobs: one workgroup per 64 KiB frame, split at the batch
+ *          launcher's threshold of ENCQ_LARGE_MIN bytes per shard into the
+ *          two variants it would pick (87 below, 76 from it up); each bucket
+ *          has the count+1 exclusive prefix sums of ceil(shard_len / 65532).
+ * Buckets come in a fixed order - small NI ascending, frame 87, frame 76 -
+ * and hold their items in caller order: at most ENCQ_BUCKETS launches. */
+constexpr uint64_t ENCQ_SMALL_MAX = 4096;
+constexpr uint64_t ENCQ_LARGE_MIN = uint64_t(1) << 20;
+constexpr int ENCQ_BUCKETS = 6;
+constexpr int ENCQ_VAR_SMALL_SHARDS = 87; /* 4 waves, nontemporal stores */
+constexpr int ENCQ_VAR_LARGE_SHARDS = 76; /* 3 waves, plain stores */
+
+struct EncBucket {
+  int kind = GFRS_EQ_SMALL, param = 0;
+  size_t first = 0, count = 0; /* items[first, first+count) */
+  size_t prefix = 0; /* frame buckets: its count+1 prefix sums start at
+                        frame_prefix[prefix] */
+};
+
+struct EncSchedule {
+  std::vector<gfrs_eitem> items;      /* every bucket's items, back to back */
+  std::vector<uint64_t> frame_prefix; /* of the frame buckets, back to back */
+  std::vector<EncBucket> buckets;
+};
+
+/* the gate of gfrs_encode_frame_batch's fused kernels, block_len aside */
+bool encode_frame_fused(const Code &c);
+/* crc32block image size of a shard at block_len 65536 */
+uint64_t encode_image_size(uint64_t shard_len);
+/* block_len of the encode queue: GFRS_ERR_INVALID_BLOCK / _UNSUPPORTED */
+int encode_queue_block_check(int64_t block_len);
+/* Job validation (gfrs.h, encode-queue contract; framed_addr = the address
+ * of framed, for the alignment rule) and the schedule. */
+int encode_queue_schedule(const gfrs_ejob *jobs, int njobs,
+                          uint64_t framed_addr, EncSchedule *out);
+
 }  // namespace gfrs
 
 #endif

@@ -218,6 +218,26 @@ class Encoder:
                                             ns, block_len),
               "encode_frame_batch")
 
+    def encode_frame_queue(self, framed, batch, jobs, block_len=65536):
+        """Encode+frame queue: encode_frame_batch per job in one call (the
+        PUT path over concurrent blobs of different sizes).  batch: flat
+        uint8 device tensor holding every job; framed: flat uint8 device
+        tensor for the images; jobs: [(off, shard_len, img_off,
+        img_stride)], shard i of a job at byte off + i*shard_len of batch,
+        the framed image of its shard j (all n+m+l of them) at byte
+        img_off + j*img_stride of framed.  Blocks until the images are
+        ready."""
+        assert batch.is_cuda and batch.is_contiguous()
+        assert framed.is_cuda and framed.is_contiguous()
+        nj = len(jobs)
+        ej = (runtime.EJob * max(1, nj))()
+        for j, (off, ln, img_off, img_stride) in enumerate(jobs):
+            ej[j] = runtime.EJob(off, ln, img_off, img_stride, 0)
+        check(lib().gfrs_encode_frame_queue(self._ctx, framed.data_ptr(),
+                                            batch.data_ptr(), ej, nj,
+                                            block_len),
+              "encode_frame_queue")
+
     def verify_batch(self, batch):
         p, ln, stride, ns = self._base(batch)
         nwords = (ns + 63) // 64

@@ -128,6 +128,39 @@ class RImage(ctypes.Structure):
     ]
 
 
+class EJob(ctypes.Structure):
+    """gfrs_ejob: one job of an encode+frame queue."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("img_off", ctypes.c_uint64),
+        ("img_stride", ctypes.c_uint64),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+
+class EItem(ctypes.Structure):
+    """gfrs_eitem: one work item of an encode+frame schedule."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("img", ctypes.c_uint64),
+        ("img_stride", ctypes.c_uint64),
+        ("job", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class EBucket(ctypes.Structure):
+    """gfrs_ebucket: one launch of an encode+frame schedule."""
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("param", ctypes.c_int32),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -246,6 +279,13 @@ def lib():
             i32p, ctypes.c_int, i64, u64p, u64p, ctypes.c_int, ctypes.c_int,
             ctypes.POINTER(RItem), u64p, ip, ctypes.POINTER(RBucket), ip,
             ctypes.POINTER(RImage), ip, i32p, i32p, i32p, u32p, i32p, ip]
+        L.gfrs_encode_frame_queue.argtypes = [vp, vp, vp,
+                                              ctypes.POINTER(EJob),
+                                              ctypes.c_int, i64]
+        L.gfrs_compute_encode_queue_schedule.argtypes = [
+            ctypes.POINTER(Tactic), ctypes.POINTER(EJob), ctypes.c_int, i64,
+            ctypes.c_int, ctypes.POINTER(EItem), u64p, ip,
+            ctypes.POINTER(EBucket), ip, ip]
         _lib = L
     return _lib
 

@@ -436,6 +436,65 @@ int gfrs_repair_queue(gfrs_ctx *ctx, void *base, const gfrs_rjob *jobs,
                       int64_t block_len, const uint64_t *bids,
                       const uint64_t *vuids, uint64_t *fail_bitmap);
 
+/* ---- encode+frame queue (stream_put.go:146 + datafile.go:342: the PUT path
+ * over concurrent blobs of different sizes) ----
+ * gfrs_encode_frame_batch as a queue: every job has its own place, shard
+ * length and image place, and gets back the n+m+l crc32block-framed images of
+ * its stripe.  jobs is host memory, base and framed device pointers.
+ *
+ * Encode-queue contract (pinned by tests/test_gpu_encode_queue.py):
+ *  - Per-job result.  For each job j the n+m+l images are byte-identical to
+ *    what gfrs_encode_frame_batch(ctx, framed + img_off, img_stride,
+ *    base + off, shard_len, <any stride>, 1, 65536) produces for that stripe
+ *    alone: the reference's Encode followed by crc32block framing of every
+ *    shard, local parities included (image of shard i at
+ *    framed + img_off + i*img_stride).
+ *  - Layout.  Sources need no alignment.  framed + img_off and img_stride are
+ *    multiples of 4.  In framed only the declared images are written: nothing
+ *    between images, nothing past an image's gfrs_crc32b_encode_size bytes.
+ *    In base nothing is written for tactics the fused kernels serve; for the
+ *    others (slow tactics, below) the parity shards of each job are written in
+ *    base, which is gfrs_encode_batch's declared output.  Overlapping jobs or
+ *    images are a caller error (not checked).
+ *  - Validation.  Everything is validated before the first launch, and any
+ *    error returns its code and writes nothing, neither in base nor in framed:
+ *      GFRS_ERR_INVALID_BLOCK for block_len <= 0 or not a multiple of 4096 (as
+ *      the batch call);
+ *      GFRS_ERR_UNSUPPORTED for any other block_len != 65536 (as
+ *      gfrs_repair_queue);
+ *      GFRS_ERR_INVALID_SHARDS for njobs <= 0, reserved != 0, a misaligned
+ *      framed + img_off or img_stride, or img_stride below the image size;
+ *      GFRS_ERR_SHARD_NO_DATA for shard_len == 0.
+ *  - Blocking.  The call blocks until the images are ready, like the other
+ *    two queues; it runs on the context stream, takes the context mutex once
+ *    and makes one upload of one blob and one sync.
+ *  - Launch bound.  For a tactic the fused kernels serve - the gate of
+ *    gfrs_encode_frame_batch: m >= 1, m + l <= 4, n + m + l <= 16 - a queue
+ *    costs at most 6 kernel launches whatever njobs is: jobs of at most 4096
+ *    bytes per shard run one wave per job, one launch per
+ *    ceil(shard_len / 1024) = 1..4; longer jobs run one workgroup per 64 KiB
+ *    frame, one launch below 1 MiB per shard and one from 1 MiB up (the two
+ *    variants the batch call picks by that threshold).
+ *  - Slow tactics.  Tactics outside that gate (RS(6+6), 17 shards, wide LRC)
+ *    run their jobs one at a time after validation, each as the composition
+ *    the batch call falls back to (gfrs_encode_batch, then
+ *    gfrs_crc32b_encode_batch of the n+m+l shards): correct, but several
+ *    launches per job. */
+typedef struct gfrs_ejob {
+  uint64_t off;        /* shard i of the job at base + off + i*shard_len,
+                          i < n+m+l (ec.Buffer layout); data shards are read */
+  uint64_t shard_len;  /* > 0, any value, no alignment */
+  uint64_t img_off;    /* framed image of shard j at
+                          framed + img_off + j*img_stride, j < n+m+l */
+  uint64_t img_stride; /* multiple of 4, >= gfrs_crc32b_encode_size(shard_len,
+                          65536) */
+  uint64_t reserved;   /* must be 0 */
+} gfrs_ejob;
+
+int gfrs_encode_frame_queue(gfrs_ctx *ctx, void *framed, void *base,
+                            const gfrs_ejob *jobs, int njobs,
+                            int64_t block_len);
+
 /* ---- ec.Buffer size math (buf.go:67-133) ---- */
 int gfrs_buffer_sizes(const gfrs_tactic *t, int64_t data_size,
                       int64_t *shard_size, int64_t *ec_data_size,
@@ -537,6 +596,42 @@ int gfrs_compute_repair_queue_schedule(
     int *nitems, gfrs_rbucket *buckets, int *nbuckets, gfrs_rimage *images,
     int *nimages, int32_t *pat_class, int32_t *pat_gm, int32_t *pat_nw,
     uint32_t *pat_colpack, int32_t *inplace_jobs, int *ninplace);
+/* GPU-free: what gfrs_encode_frame_queue would upload for a queue, with the
+ * same builder, so CPU tests can check it without a device.
+ *   Job classes: a job of at most 4096 bytes per shard is SMALL and runs one
+ *   wave (param = NI = ceil(shard_len / 1024), 1..4: one bucket per NI); a
+ *   longer job is a FRAME job and runs one workgroup per 64 KiB frame (param =
+ *   the batch launcher's variant for its length: 87 - 4 waves, nontemporal
+ *   stores - below 1 MiB per shard, 76 - 3 waves, plain stores - from 1 MiB).
+ *   Buckets: at most 6, in the fixed order small NI ascending, then frame 87,
+ *   then frame 76; bucket b owns items[first, first+count), in caller order.
+ *   Prefix sums: only frame buckets have them.  The q-th frame bucket (q = 0
+ *   or 1) owns the count+1 exclusive prefix sums of ceil(shard_len / 65532) at
+ *   frame_prefix[first - nsmall + q ...], nsmall being the number of small
+ *   items (all of which precede the frame items).
+ * *fused tells whether the tactic passes the gate of the fused kernels; when
+ * it is 0 the engine ignores the schedule and runs the jobs one at a time.
+ * items holds item_cap entries, frame_prefix item_cap + 2, buckets 6
+ * (GFRS_ERR_NOMEM when the schedule is larger).  Returns the validation codes
+ * of gfrs_encode_frame_queue, taking framed as 4-aligned. */
+enum { GFRS_EQ_SMALL = 0, GFRS_EQ_FRAME = 1 };
+typedef struct gfrs_eitem {
+  uint64_t off, shard_len; /* of the job */
+  uint64_t img;            /* byte offset in framed of the image of shard 0 */
+  uint64_t img_stride;     /* between the job's images */
+  int32_t job;             /* caller's index */
+  int32_t reserved;
+} gfrs_eitem;
+typedef struct gfrs_ebucket {
+  int32_t kind, param, first, count;
+} gfrs_ebucket;
+int gfrs_compute_encode_queue_schedule(const gfrs_tactic *t,
+                                       const gfrs_ejob *jobs, int njobs,
+                                       int64_t block_len, int item_cap,
+                                       gfrs_eitem *items,
+                                       uint64_t *frame_prefix, int *nitems,
+                                       gfrs_ebucket *buckets, int *nbuckets,
+                                       int *fused);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);

@@ -1,0 +1,269 @@
+"""Encode+frame queues for the gfrs_encode_frame_queue tests.
+
+A queue is what the access gateway's PUT path sees: concurrent blobs of
+different sizes, each to be encoded and framed into its n+m+l crc32block
+images.  Everything the GPU module (tests/test_gpu_encode_queue.py) feeds to
+the engine is generated here, so tests/test_encode_queue_cpu.py can check the
+same queues against the schedule builder and against the oracle alone.
+
+Expectations come from the oracle only: pyoracle.rs_encode / lrc_encode of
+the job's data shards, then pyoracle.crc32b_encode of every shard - never
+from the engine.
+
+Shard lengths are the smallest at which each path can still go wrong
+(16-byte vectors, 1024-byte wave pieces, 4096-byte class edge and workgroup
+pieces, 16384-byte passes, 65532-byte frame payloads, the 1 MiB variant
+threshold):
+  small  1, 15, 16, 17          ragged tail only / one vector / vector + tail
+         1023, 1024, 1025       NI 1 -> 2
+         2048, 3073             NI 2 full; one byte into the fourth piece
+         4095, 4096             the class edge
+         2049, 3072             (added here) the list above has no NI = 3 job
+  frame  4097, 8209             class edge; two pieces + vector + ragged byte
+         16383, 16385, 49153    pass edge; one byte into the fourth pass
+         65531, 65532, 65533    one byte short of / exactly / past a frame
+         65596, 65597           a trailing frame of 64 and of 65 bytes (the
+                                batch kernel folds the first, not the second)
+         131064, 131065         two exact frames; and a third of one byte
+  large  1048576, 1048577       the bucket of the 3-wave variant
+"""
+import ctypes
+import functools
+
+import _arena as A
+import _verdict as V
+from _arena import L, Arena, oracle, vp
+
+from cubefs_amd import runtime
+from cubefs_amd.ec import _tactic_struct
+
+SMALL = [1, 15, 16, 17, 1023, 1024, 1025, 2048, 3073, 4095, 4096]
+FRAME = [4097, 8209, 16383, 16385, 49153, 65531, 65532, 65533, 65596, 65597,
+         131064, 131065]
+LARGE = [1048576, 1048577]
+NI3 = [2049, 3072]      # ceil(len / 1024) == 3: the one NI the lists miss
+PAYLOAD = 65532
+SMALL_MAX = 4096
+LARGE_MIN = 1 << 20
+KIND_SMALL, KIND_FRAME = 0, 1
+VAR_BELOW, VAR_FROM = 87, 76     # the batch launcher's variants
+MAX_BUCKETS = 6
+GAPS = [1, 3, 7, 5, 11, 1, 9, 3, 13, 7, 5]   # odd bytes between jobs
+ERR_NO_DATA, ERR_INVALID, ERR_BLOCK, ERR_NOMEM, ERR_UNSUPPORTED = \
+    -4, -6, -10, -102, -103
+
+
+def frames(slen):
+    return (slen + PAYLOAD - 1) // PAYLOAD
+
+
+def round4(n):
+    return (n + 3) // 4 * 4
+
+
+def bucket_of(slen):
+    """(kind, param) the schedule must give a job of this length."""
+    if slen <= SMALL_MAX:
+        return KIND_SMALL, (slen + 1023) // 1024
+    return KIND_FRAME, VAR_BELOW if slen < LARGE_MIN else VAR_FROM
+
+
+def interleave(*lists):
+    """Round-robin over the lists, each walked from both ends in turn, so
+    neighbours in the queue - and in a bucket - differ in length."""
+    out = []
+    pools = [list(x) for x in lists]
+    turn = 0
+    while any(pools):
+        for p in pools:
+            if p:
+                out.append(p.pop(0) if turn % 2 == 0 else p.pop())
+        turn += 1
+    return out
+
+
+class EQueue:
+    """jobs[j] = (off, slen, img_off, img_stride); data[j] = the oracle's
+    (total, slen) stripe of job j (read-only)."""
+
+    def __init__(self, name, t, lens, delta=1):
+        self.name, self.t = name, t
+        self.total = t.N + t.M + t.L
+        self.delta = delta
+        n = len(lens)
+        need, seen = {}, {}
+        for slen in lens:
+            need[slen] = need.get(slen, 0) + 1
+        self.data, src = [], []
+        off = 0
+        for j, slen in enumerate(lens):
+            ref = A.ref_stripes(t, need[slen], slen, seed=31)
+            s = seen.get(slen, 0)
+            seen[slen] = s + 1
+            self.data.append(ref[s])
+            src.append(off)
+            off += self.total * slen + GAPS[j % len(GAPS)]
+        self.nbytes = src[-1] + self.total * lens[-1]
+        # image order is not job order: odd jobs first, then the even ones
+        # backwards; uneven 4-aligned padding; tight stride for odd jobs,
+        # padded for even ones
+        place = [None] * n
+        at = end = 0
+        order = [j for j in range(n) if j % 2] + \
+            [j for j in range(n) if j % 2 == 0][::-1]
+        for j in order:
+            size = A.enc_size(lens[j])
+            stride = round4(size) + (0 if j % 2 else 4 * (1 + j % 3))
+            place[j] = (at, stride)
+            end = at + (self.total - 1) * stride + size
+            at = round4(end) + 4 * ((5 * j) % 4)
+        self.img_bytes = end     # the arena ends with the last image placed
+        self.jobs = [(src[j], lens[j]) + place[j] for j in range(n)]
+
+    def image_regions(self, j):
+        """[(offset in framed, size)] of job j's n+m+l images."""
+        _, slen, img_off, stride = self.jobs[j]
+        return [(img_off + i * stride, A.enc_size(slen))
+                for i in range(self.total)]
+
+
+@functools.lru_cache(maxsize=None)
+def build(name):
+    if name == "rs63_mixed":
+        return EQueue(name, V.get_tactic("EC6P3"),
+                      interleave(SMALL, FRAME, LARGE + NI3))
+    if name == "rs63_small":
+        # small class only.  91 jobs: with the grid forced to 1 or 3, every
+        # NI bucket holds more jobs than 4 x grid waves (14 at the least)
+        lens = SMALL + NI3
+        return EQueue(name, V.get_tactic("EC6P3"),
+                      [lens[(5 * j) % len(lens)] for j in range(91)])
+    if name == "rs42":
+        return EQueue(name, V.get_tactic("EC4P2"),
+                      interleave(SMALL + NI3, FRAME))
+    if name == "rs124_k12":
+        return EQueue(name, V.get_tactic("EC12P4"),
+                      interleave(FRAME, SMALL + NI3))
+    if name == "lrc_fused":
+        return EQueue(name, A.lrc_tactic(), interleave(SMALL + NI3, FRAME))
+    if name == "rs66_slow":
+        # RS(6+6): six rows do not fit the fused kernels; one job at a time
+        return EQueue(name, V.get_tactic("EC6P6"),
+                      [17, 4097, 65533, 1024, 16, 65597, 1, 131064, 16383,
+                       2048, 4096, 8209])
+    raise KeyError(name)
+
+
+FUSED_QUEUES = ["rs63_mixed", "rs63_small", "rs42", "rs124_k12", "lrc_fused"]
+GPU_QUEUES = FUSED_QUEUES + ["rs66_slow"]
+
+
+@functools.lru_cache(maxsize=None)
+def expectations(name):
+    """Per job: the n+m+l framed images, oracle.crc32b_encode of the
+    oracle-encoded stripe."""
+    q = build(name)
+    return [[oracle.crc32b_encode(q.data[j][i].copy())
+             for i in range(q.total)] for j in range(len(q.jobs))]
+
+
+def fused_gate(t):
+    """The gate of gfrs_encode_frame_batch's fused kernels (include/gfrs.h)."""
+    return t.M >= 1 and t.M + t.L <= 4 and t.N + t.M + t.L <= 16
+
+
+# ---- C ABI arguments --------------------------------------------------------
+
+def ejob_array(jobs):
+    """jobs: (off, slen, img_off, img_stride[, reserved])."""
+    arr = (runtime.EJob * max(1, len(jobs)))()
+    for j, job in enumerate(jobs):
+        arr[j] = runtime.EJob(job[0], job[1], job[2], job[3],
+                              job[4] if len(job) > 4 else 0)
+    return arr
+
+
+# ---- schedule (GPU-free export) ---------------------------------------------
+
+class Schedule:
+    pass
+
+
+def schedule(t, jobs, block_len=A.BLOCK, item_cap=None):
+    """gfrs_compute_encode_queue_schedule -> (rc, Schedule or None)."""
+    nj = len(jobs)
+    item_cap = nj if item_cap is None else item_cap
+    items = (runtime.EItem * max(1, item_cap))()
+    prefix = (ctypes.c_uint64 * (max(1, item_cap) + 2))()
+    buckets = (runtime.EBucket * MAX_BUCKETS)()
+    ni, nb, fused = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(-1)
+    ts = _tactic_struct(t)
+    rc = L().gfrs_compute_encode_queue_schedule(
+        ctypes.byref(ts), ejob_array(jobs), nj, block_len, item_cap, items,
+        prefix, ctypes.byref(ni), buckets, ctypes.byref(nb),
+        ctypes.byref(fused))
+    if rc != 0:
+        return rc, None
+    s = Schedule()
+    s.items = [(i.job, i.off, i.shard_len, i.img, i.img_stride, i.reserved)
+               for i in items[:ni.value]]
+    s.buckets = [(b.kind, b.param, b.first, b.count)
+                 for b in buckets[:nb.value]]
+    nframe = sum(1 for b in s.buckets if b[0] == KIND_FRAME)
+    nfitems = sum(b[3] for b in s.buckets if b[0] == KIND_FRAME)
+    s.prefix = list(prefix[:nfitems + nframe])
+    s.fused = fused.value
+    return 0, s
+
+
+# ---- GPU runner: one call, both arenas checked ------------------------------
+
+def load(q, dev, seed=90):
+    """(base arena with the data shards only, image arena), both uploaded.
+    The parity regions of base stay random: the fused kernels must neither
+    read nor write them."""
+    src = Arena(dev, q.nbytes, q.delta, seed=seed)
+    for j, (off, slen, _, _) in enumerate(q.jobs):
+        for i in range(q.t.N):
+            src.put(off + i * slen, q.data[j][i])
+    src.upload()
+    dst = Arena(dev, q.img_bytes, 4, seed=seed + 1)
+    dst.upload()
+    return src, dst
+
+
+def call(enc, src, dst, q, jobs=None, block_len=A.BLOCK, njobs=None,
+         dst_shift=0):
+    jobs = q.jobs if jobs is None else jobs
+    return L().gfrs_encode_frame_queue(
+        enc._ctx, vp(dst.ptr + dst_shift), vp(src.ptr), ejob_array(jobs),
+        len(jobs) if njobs is None else njobs, block_len)
+
+
+def check(q, src, dst, what="", jobs=None):
+    """framed: the oracle's images and not one other byte changed.  base:
+    unchanged for a fused tactic; for a slow one the parity shards - and
+    nothing else - hold the oracle's parity."""
+    exp = expectations(q.name)
+    want = dst.expect()
+    for j in (range(len(q.jobs)) if jobs is None else jobs):
+        for (off, size), img in zip(q.image_regions(j), exp[j]):
+            assert img.size == size
+            dst.put(off, img, want)
+    dst.check(want, what=what + " images")
+    want = src.expect()
+    if not fused_gate(q.t):
+        for j, (off, slen, _, _) in enumerate(q.jobs):
+            for i in range(q.t.N, q.total):
+                src.put(off + i * slen, q.data[j][i], want)
+    src.check(want, what=what + " base")
+
+
+def run(dev, name, what=""):
+    q = build(name)
+    enc = A.encoder(q.t)
+    src, dst = load(q, dev)
+    what = "%s encode queue %s" % (what, name)
+    A.ok(call(enc, src, dst, q), what)
+    check(q, src, dst, what)
+    return src, dst

@@ -19,6 +19,20 @@ gfrs_repair_batch:
  (e) mixed    the 4096-job queue of (b), [6] in place of the verify-only
      pattern: the queue vs a loop of single-job gfrs_repair_batch calls.
 
+and gfrs_encode_frame_queue against gfrs_encode_frame_batch, RS(6+3)
+(--only fpghi, p standing for f'):
+
+ (f) uniform  1024 jobs x 8 MiB, the headline PUT shape: the queue vs ONE
+     batch call, three interleaved medians of each.
+ (f') the same with 64 KiB shards, whose trailing 4-byte frame the batch
+     kernel folds into the preceding workgroup and the queue kernel does not.
+ (g) mixed    4096 jobs of 64 KiB / 1 MiB / 4 MiB: the queue vs a loop of
+     single-job batch calls, and vs one batch call per distinct size.
+ (h) small    65536 jobs x 2 KiB: the queue vs ONE batch call, both on the
+     wave-per-stripe kernel (the cost of the per-job operator setup).
+ (i) 65536 jobs x 6 KiB: the batch call runs the wave kernel there, the
+     queue the frame kernel.
+
 (a) and (d) run on random data with encoded parity; the others on a zeroed buffer
 (a valid stripe: zero parity), since the kernels' work does not depend on
 the data.  One JSON line on stdout; --out also writes it to a file.
@@ -266,17 +280,163 @@ class Probe:
         return res
 
 
+class EncodeProbe:
+    """gfrs_encode_frame_queue against gfrs_encode_frame_batch, RS(6+3), on
+    zeroed sources (the kernels' work does not depend on the data).  The
+    batch call returns with its work queued, so every yardstick ends with
+    gfrs_synchronize; the queue call blocks by itself."""
+
+    def __init__(self):
+        self.t = codemode.get_tactic("EC6P3")
+        self.enc = ec.Encoder(self.t)
+        self.L = runtime.lib()
+        self.total = self.t.N + self.t.M
+
+    def layout(self, lens):
+        """ec.Buffer stripes back to back; images back to back at the tight
+        4-aligned stride."""
+        jobs, off, img = [], 0, 0
+        for ln in lens:
+            stride = (self.L.gfrs_crc32b_encode_size(ln, 65536) + 3) // 4 * 4
+            jobs.append((off, ln, img, stride))
+            off += self.total * ln
+            img += self.total * stride
+        return jobs, off, img
+
+    def buffers(self, lens):
+        jobs, nbytes, nimg = self.layout(lens)
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        dst = torch.empty(nimg, dtype=torch.uint8, device="cuda")
+        ej = (runtime.EJob * len(jobs))()
+        for j, (off, ln, img, stride) in enumerate(jobs):
+            ej[j] = runtime.EJob(off, ln, img, stride, 0)
+        return jobs, buf, dst, ej
+
+    def queue(self, buf, dst, ej, njobs):
+        rc = self.L.gfrs_encode_frame_queue(self.enc._ctx, dst.data_ptr(),
+                                            buf.data_ptr(), ej, njobs, 65536)
+        assert rc == 0, rc
+
+    def batch(self, buf, dst, job, nstripes):
+        off, ln, img, stride = job
+        rc = self.L.gfrs_encode_frame_batch(
+            self.enc._ctx, dst.data_ptr() + img, stride, buf.data_ptr() + off,
+            ln, self.total * ln, nstripes, 65536)
+        assert rc == 0, rc
+
+    def uniform(self, njobs, slen, reps):
+        """(f), (f'), (h), (i): the queue vs ONE gfrs_encode_frame_batch over
+        the same buffers; three medians of each, interleaved, so that the
+        batch call's own run-to-run spread is on record next to the
+        difference."""
+        jobs, buf, dst, ej = self.buffers([slen] * njobs)
+
+        def batch():
+            self.batch(buf, dst, jobs[0], njobs)
+            self.enc.synchronize()
+
+        res = {"njobs": njobs, "shard_len": slen}
+        for i in (1, 2, 3):
+            res["batch_%d" % i] = timed(batch, reps)
+            res["queue_%d" % i] = timed(
+                lambda: self.queue(buf, dst, ej, njobs), reps)
+        bs = [res["batch_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        qs = [res["queue_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        res["batch_medians_ms"], res["queue_medians_ms"] = bs, qs
+        res["batch_spread"] = round(max(bs) / min(bs) - 1, 4)
+        res["queue_over_batch"] = round(statistics.median(qs) /
+                                        statistics.median(bs), 4)
+        res["moved_GB"] = round(njobs * slen * (self.t.N + self.total) / 1e9,
+                                3)
+        return res
+
+    def mixed(self, lens, reps, loop_reps):
+        """(g): the queue vs a loop of single-job batch calls, and vs one
+        batch call per distinct size (what a size-sorting shim would issue:
+        the same bytes, regrouped by size over the same buffers)."""
+        jobs, buf, dst, ej = self.buffers(lens)
+
+        def loop():
+            for job in jobs:
+                self.batch(buf, dst, job, 1)
+            self.enc.synchronize()
+
+        groups, off, img = [], 0, 0
+        for ln in sorted(set(lens)):
+            n = lens.count(ln)
+            stride = (self.L.gfrs_crc32b_encode_size(ln, 65536) + 3) // 4 * 4
+            groups.append(((off, ln, img, stride), n))
+            off += n * self.total * ln
+            img += n * self.total * stride
+
+        def per_size():
+            for job, n in groups:
+                self.batch(buf, dst, job, n)
+            self.enc.synchronize()
+
+        res = {"njobs": len(jobs), "bytes": buf.numel(),
+               "image_bytes": dst.numel(), "sizes": len(groups)}
+        for i in (1, 2, 3):
+            res["per_size_%d" % i] = timed(per_size, reps)
+            res["queue_%d" % i] = timed(
+                lambda: self.queue(buf, dst, ej, len(jobs)), reps)
+        res["loop"] = timed(loop, loop_reps)
+        ps = [res["per_size_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        qs = [res["queue_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        res["per_size_medians_ms"], res["queue_medians_ms"] = ps, qs
+        res["per_size_spread"] = round(max(ps) / min(ps) - 1, 4)
+        res["queue_over_per_size"] = round(statistics.median(qs) /
+                                           statistics.median(ps), 4)
+        res["loop_over_queue"] = round(res["loop"]["median_ms"] /
+                                       statistics.median(qs), 2)
+        return res
+
+
+def encode_main(a, out):
+    p = EncodeProbe()
+    out["encode_tactic"] = "EC6P3"
+    if "f" in a.only:
+        out["f_encode_uniform"] = p.uniform(1024 // a.scale, 8 * MIB, reps=7)
+        torch.cuda.empty_cache()
+    if "p" in a.only:                        # (f') in the documents
+        out["f2_encode_uniform_64k"] = p.uniform(1024 // a.scale, 64 * KIB,
+                                                 reps=7)
+        torch.cuda.empty_cache()
+    if "g" in a.only:
+        rng = random.Random(7)
+        lens = [rng.choice([64 * KIB, MIB, 4 * MIB])
+                for _ in range(4096 // a.scale)]
+        out["g_encode_mixed"] = p.mixed(lens, reps=5, loop_reps=3)
+        torch.cuda.empty_cache()
+    if "h" in a.only:
+        out["h_encode_small"] = p.uniform(65536 // a.scale, 2 * KIB, reps=7)
+        torch.cuda.empty_cache()
+    if "i" in a.only:
+        out["i_encode_6k"] = p.uniform(65536 // a.scale, 6 * KIB, reps=7)
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--scale", type=int, default=1,
                     help="divide every job count by this (dry runs)")
     ap.add_argument("--only", default="abcde",
-                    help="which configurations to run, e.g. 'ac'")
+                    help="which configurations to run, e.g. 'ac'; the "
+                    "encode+frame queue's are 'fpghi' (p = f')")
     a = ap.parse_args()
+    out = {"device": torch.cuda.get_device_name(0), "scale": a.scale}
+    if set(a.only) & set("fpghi"):
+        encode_main(a, out)
+    if not set(a.only) & set("abcde"):
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     p = Probe()
-    out = {"device": torch.cuda.get_device_name(0), "tactic": "EC12P4",
-           "scale": a.scale}
+    out["tactic"] = "EC12P4"
     for name in ("GFRS_RS_SEQ", "GFRS_RS_GRID"):
         if name in os.environ:
             out[name] = os.environ[name]
