@@ -26,6 +26,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 namespace gfrs {
 
@@ -2189,6 +2190,435 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_reg_k(
 
 
 /* ------------------------------------------------------------------ */
+/* aligned fused encode+frame: destination-space chunks, DPP rotation   */
+/* ------------------------------------------------------------------ */
+
+/* A 65536-B frame image is 4096 aligned 16-B chunks: chunk 0 is
+ * [crc | first 12 payload bytes], chunks 1..4095 are payload.  This kernel
+ * lays the lane-piece map out in DESTINATION space, so every lane-piece is
+ * one aligned uint4 store, and loads one ALIGNED source uint4 per piece:
+ * image chunk q of frame f holds shard bytes [p0 + 16q - 4, +16), p0 =
+ * f*65532, which start r = (3f - 1) mod 4 dwords into the aligned source
+ * chunk L_q at shard offset p0 - 4 - 4r + 16q.  The image chunk is the
+ * upper 4-r dwords of L_q followed by the lower r dwords of L_{q+1}, and
+ * L_{q+1} is what the NEXT lane loaded: the rotation is r neighbour-lane
+ * DPP moves (wave_shl:1, VALU rate, no LDS), done once straight after the
+ * load so MAC, CRC and stores all run in destination space (the GF MAC is
+ * bytewise: parity accumulators come out destination-aligned).
+ *
+ * Piece map (wave-contiguous): in pass h (1024 chunks) wave w owns chunks
+ * [1024h + 256w, +256), piece i of lane l is chunk 1024h + 256w + 64i + l.
+ * Lane 63's donor for pieces 0..2 is lane 0 of the same wave's next piece,
+ * already in registers (one wave_rol:1 move feeds it in as the DPP `old`
+ * operand); only piece 3 needs one extra ONE-LANE load per unit (lane 63,
+ * 12 B).  The lane's pieces are 1024 B apart: Horner chain via g_shift1k.
+ *
+ * Eligibility (host): dst, dst_stride, base, stripe_stride and shard_len
+ * all multiples of 16.  Then every L_q is 16-B aligned in memory and shard
+ * ends are 16-B aligned too, so an aligned chunk that holds at least one
+ * needed byte lies wholly inside its shard: loads are masked by exactly
+ * that rule and never leave the caller's buffer (the one chunk before
+ * frame 0 only carries the header slot and is masked).
+ *
+ * CRC: the header dword of chunk 0 is zeroed in registers; leading zeros
+ * do not change the raw zero-init CRC, so the message is the image bytes
+ * [0, 4 + payload) and the position operators are image-relative.
+ * C0: 0 = chunk 0's 12 payload bytes are stored early (dwordx3 at +4) and
+ * the header dword in the epilogue; 1 = they wait in LDS and the epilogue
+ * writes [crc | 12 B] as one aligned uint4. */
+typedef uint32_t u32x3a __attribute__((ext_vector_type(3)));
+struct AlLd {
+  uint4 v[4];
+  u32x3a e; /* lane 63: low dwords of the chunk after its piece 3 */
+};
+
+/* aligned piece loads of one unit; sp = shard + p0 - 4 - 4r (chunk 0).
+ * FULL = a whole 65532-B frame: only chunk 0 under r = 3 is masked. */
+template <bool FULL>
+GFRS_DEV AlLd al_load(const uint8_t *sp, int r, int P, int nfull, int q0) {
+  AlLd o;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int q = q0 + 64 * i;
+    const bool lm = FULL ? (i > 0 || q > 0 || r < 3)
+                         : (q <= nfull && 16 * q - 4 - 4 * r < P &&
+                            16 * q + 12 - 4 * r > 0);
+    o.v[i] = lm ? *reinterpret_cast<const uint4 *>(sp + 16 * q)
+                : uint4{0, 0, 0, 0};
+  }
+  const int qe = q0 + 193; /* lane 63: the chunk after its piece 3 */
+  const bool em = (threadIdx.x & 63) == 63 && r > 0 &&
+                  (FULL || (qe <= nfull && 16 * qe - 4 - 4 * r < P));
+  o.e = em ? *reinterpret_cast<const u32x3a *>(sp + 16 * qe)
+           : u32x3a{0, 0, 0};
+  return o;
+}
+
+/* lane l <- lane l+1 of `own`; lane 63 <- `edge` */
+GFRS_DEV uint32_t al_shl1(uint32_t edge, uint32_t own) {
+  return uint32_t(__builtin_amdgcn_update_dpp(int(edge), int(own),
+                                              0x130 /* wave_shl:1 */, 0xF,
+                                              0xF, false));
+}
+/* lane 63 <- lane 0 (other lanes unused) */
+GFRS_DEV uint32_t al_rol1(uint32_t v) {
+  return uint32_t(__builtin_amdgcn_update_dpp(0, int(v),
+                                              0x134 /* wave_rol:1 */, 0xF,
+                                              0xF, false));
+}
+
+/* gf2_mulmod_d, branch-free and fully unrolled: the per-unit fold by the
+ * lane's position operator is ~40% of a unit's VALU work in the looped
+ * compare/select form; as sign-extended bit masks it is ~6 VALU per bit */
+GFRS_DEV uint32_t al_mulmod(uint32_t a, uint32_t b) {
+  uint32_t prod = 0;
+#pragma unroll
+  for (int i = 31; i >= 0; i--) {
+    const uint32_t ma = uint32_t(int32_t(a << (31 - i)) >> 31);
+    prod ^= b & ma;
+    const uint32_t mb = uint32_t(int32_t(b << 31) >> 31);
+    b = (b >> 1) ^ (CRC_POLY & mb);
+  }
+  return prod;
+}
+
+/* XOR over the 64 lanes without LDS: two quad swaps and the two row
+ * mirrors leave every lane with its 16-lane row's total; the four rows
+ * meet in scalar registers.  All lanes must be active. */
+GFRS_DEV uint32_t al_wave_xor(uint32_t x) {
+  x ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0xB1 /* quad_perm:
+      [1,0,3,2] */, 0xF, 0xF, true));
+  x ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x4E /* quad_perm:
+      [2,3,0,1] */, 0xF, 0xF, true));
+  x ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(x),
+                                            0x141 /* row_half_mirror */, 0xF,
+                                            0xF, true));
+  x ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x140 /* row_mirror */,
+                                            0xF, 0xF, true));
+  return uint32_t(__builtin_amdgcn_readlane(int(x), 0) ^
+                  __builtin_amdgcn_readlane(int(x), 16) ^
+                  __builtin_amdgcn_readlane(int(x), 32) ^
+                  __builtin_amdgcn_readlane(int(x), 48));
+}
+
+template <int R>
+GFRS_DEV void al_rot(uint4 (&d)[4], const AlLd &c) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const uint4 own = c.v[i];
+    uint32_t n[3] = {0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      const uint32_t ownj = j == 0 ? own.x : j == 1 ? own.y : own.z;
+      uint32_t edge;
+      if (i < 3) {
+        const uint4 nx = c.v[i < 3 ? i + 1 : 3];
+        edge = al_rol1(j == 0 ? nx.x : j == 1 ? nx.y : nx.z);
+      } else {
+        edge = j == 0 ? c.e.x : j == 1 ? c.e.y : c.e.z;
+      }
+      n[j] = al_shl1(edge, ownj);
+    }
+    d[i] = R == 0   ? own
+           : R == 1 ? uint4{own.y, own.z, own.w, n[0]}
+           : R == 2 ? uint4{own.z, own.w, n[0], n[1]}
+                    : uint4{own.w, n[0], n[1], n[2]};
+  }
+}
+
+template <int GM, int WPS, int SKEL = 0, int ST = 0, int C0 = 0>
+__global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
+    uint8_t *__restrict__ dst, size_t dst_stride, uint64_t base,
+    uint64_t stripe_stride, size_t shard_len, int k,
+    const uint8_t *__restrict__ tabs /* [GM*k][32] */, int64_t total_frames,
+    int64_t frames_per_shard, int tiny_len /* as rs_encode_frame_reg_k */) {
+  constexpr int64_t block_len = 65536;
+  constexpr int payload_full = 65532;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  /* crc tables 8 KB | shift1k 4 KB | red slab | x8tab | tailb | tinyb |
+   * chunk-0 slab (16 x 16 B) | coefficient tables */
+  uint32_t(*tab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem);
+  uint32_t(*stab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem + 8192);
+  uint32_t *red = reinterpret_cast<uint32_t *>(smem + 12288);
+  uint32_t *x8tab = reinterpret_cast<uint32_t *>(smem + 12288 + EF_RED);
+  uint8_t *tailb = smem + 12288 + EF_RED + 64;
+  uint8_t *tinyb = smem + 12288 + EF_RED + 64 + 256; /* 16 x 64 */
+  uint32_t *c0b =
+      reinterpret_cast<uint32_t *>(smem + 12288 + EF_RED + 64 + 256 + 1024);
+  uint8_t *ctab = smem + 12288 + EF_RED + 64 + 256 + 1024 + 256;
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift1k[0][0])[i];
+  for (int i = threadIdx.x; i < GM * k * 2; i += CRC_BLOCKT)
+    reinterpret_cast<uint4 *>(ctab)[i] =
+        reinterpret_cast<const uint4 *>(tabs)[i];
+  if (threadIdx.x == 0) {
+    uint32_t v = 0x80000000u;
+    for (int j = 0; j < 16; j++) {
+      x8tab[j] = v;
+      v = gf2_mulmod_d(v, g_pow8[0]);
+    }
+  }
+  const int tid = int(threadIdx.x);
+  /* lane's piece-0 chunk within a pass: wave-contiguous map */
+  const int ql0 = (tid >> 6) * 256 + (tid & 63);
+  /* full-frame fold operators: all four pieces are always valid, the
+   * suffix after the lane's last piece of pass 0 is 65536 - 16*(ql0+193) */
+  constexpr uint32_t INV16K = 0x479933FCu;
+  const uint32_t op_pA = x8n_d(uint64_t(65536 - 16 * (ql0 + 192 + 1)));
+  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
+  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
+  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  const uint32_t it_full =
+      gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
+  __syncthreads();
+
+  const int64_t fr0 = blockIdx.x, frS = gridDim.x;
+  int64_t stripe = fr0 / frames_per_shard;
+  int64_t f = fr0 - stripe * frames_per_shard;
+  const int64_t dstripe = frS / frames_per_shard;
+  const int64_t drem = frS - dstripe * frames_per_shard;
+  AlLd nx = {};
+  if (fr0 < total_frames) { /* later frames are prefetched by the previous
+                               frame's last pass */
+    const int64_t p0 = f * payload_full;
+    const int r = int((3 * f + 3) & 3);
+    const int P = int(i64min(payload_full, int64_t(shard_len) - p0));
+    nx = al_load<false>(
+        as_global(base + stripe * stripe_stride) + (p0 - 4 - 4 * r), r, P,
+        (P + 4) >> 4, ql0);
+  }
+  for (int64_t fr = fr0; fr < total_frames; fr += frS) {
+    /* (stripe, f) of this block's next frame, tracked incrementally */
+    int64_t stripe2 = stripe + dstripe, f2 = f + drem;
+    if (f2 >= frames_per_shard) {
+      f2 -= frames_per_shard;
+      ++stripe2;
+    }
+    const int64_t p0 = f * payload_full;
+    const int r = int((3 * f + 3) & 3); /* (3f - 1) mod 4 */
+    const int P = int(i64min(payload_full, int64_t(shard_len) - p0));
+    const int T = P + 4;          /* image bytes of this frame */
+    const int nfull = T >> 4;     /* whole chunks */
+    const int tb = T & 15;        /* trailing bytes (0, 4, 8 or 12) */
+    const int ntot = (T + 15) >> 4;
+    const int64_t abase = p0 - 4 - 4 * r; /* shard offset of L_0 */
+    const uint8_t *sbase = as_global(base + stripe * stripe_stride);
+
+    for (int j = threadIdx.x; j < 64; j += CRC_BLOCKT) red[j] = 0;
+    __syncthreads();
+
+    /* the four passes; FULL (a whole 65532-B frame, the common case) drops
+     * every per-piece validity branch and the tail, so the four pieces of
+     * a unit are one straight-line block the scheduler can interleave */
+    auto passes = [&](auto fullc) {
+    constexpr bool FULL = decltype(fullc)::value;
+    uint4 acc[GM][4];
+    for (int h = 0; h < 4; h++) {
+      if (!FULL && 1024 * h >= ntot) break;
+      const int qp = 1024 * h + ql0; /* lane's piece-0 chunk */
+      const bool tail = !FULL && tb != 0 && (nfull >> 10) == h;
+#pragma unroll
+      for (int rr = 0; rr < GM; rr++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[rr][i] = uint4{0, 0, 0, 0};
+
+      uint32_t op = h == 0   ? op_pA
+                    : h == 1 ? op_pB
+                    : h == 2 ? op_pC
+                             : op_pD;
+      if (!FULL) {
+        int np = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (qp + 64 * i < nfull) np = i + 1;
+        const int end = np ? 16 * (qp + 64 * (np - 1) + 1) : 0;
+        op = x8n_d(uint64_t(T - end));
+      }
+
+      for (int c = 0; c < k; c++) {
+        const uint8_t *src = sbase + size_t(c) * shard_len;
+        uint8_t *fdst =
+            dst + (stripe * (k + GM) + c) * dst_stride + f * block_len;
+        LinTab lt[GM];
+        if (SKEL != 1)
+#pragma unroll
+          for (int rr = 0; rr < GM; rr++)
+            lt[rr] = lintab_load(ctab, rr * k + c);
+        const AlLd cur = nx;
+        if (c + 1 < k)
+          nx = al_load<FULL>(src + shard_len + abase, r, P, nfull, qp);
+        /* rotate into destination space: all lanes active here (DPP
+         * reads neighbour lanes), masked pieces carry zeros */
+        uint4 d[4];
+        switch (r) {
+          case 0: al_rot<0>(d, cur); break;
+          case 1: al_rot<1>(d, cur); break;
+          case 2: al_rot<2>(d, cur); break;
+          default: al_rot<3>(d, cur); break;
+        }
+        if (qp == 0) d[0].x = 0; /* header slot of chunk 0 */
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int q = qp + 64 * i;
+          if (FULL || q < nfull) {
+            const uint4 v = d[i];
+            if (SKEL != 1) {
+#pragma unroll
+              for (int dd = 0; dd < 4; dd++)
+                gfmac4_lin_rows<GM>(acc, i, dd, (&v.x)[dd], lt);
+            }
+            if (i == 0 && q == 0) {
+              if (C0 == 0) {
+                *reinterpret_cast<u32x3a *>(fdst + 4) =
+                    u32x3a{v.y, v.z, v.w};
+              } else {
+                c0b[c * 4 + 1] = v.y;
+                c0b[c * 4 + 2] = v.z;
+                c0b[c * 4 + 3] = v.w;
+              }
+            } else {
+              fstore16<ST>(fdst + 16 * q, v);
+            }
+            if (SKEL != 1) t = shift4k(t, stab) ^ crc16_reg(v, tab);
+          }
+        }
+        uint32_t part = al_mulmod(op, t);
+        if (tail) {
+          /* lane-parallel tail: one byte per lane at image offset p */
+          const int p = 16 * nfull + tid;
+          if (p < T) {
+            const uint8_t x = src[p0 + p - 4];
+            fdst[p] = x;
+            tailb[c * 16 + tid] = x;
+            if (SKEL != 1)
+              part ^= gf2_mulmod_d(x8tab[T - 1 - p], tab[0][x]);
+          }
+        }
+        part = al_wave_xor(part);
+        if ((tid & 63) == 0) red[(tid >> 6) * 16 + c] ^= part;
+      }
+      if (tail) __syncthreads(); /* tailb visible to all */
+      { /* next pass's (or next frame's) unit-0 loads fly during the
+           parity rows and the frame epilogue */
+        if (FULL ? h < 3 : 1024 * (h + 1) < ntot) {
+          nx = al_load<FULL>(sbase + abase, r, P, nfull, qp + 1024);
+        } else if (fr + frS < total_frames) {
+          const int64_t p02 = f2 * payload_full;
+          const int r2 = int((3 * f2 + 3) & 3);
+          const int P2 = int(i64min(payload_full, int64_t(shard_len) - p02));
+          nx = al_load<false>(as_global(base + stripe2 * stripe_stride) +
+                                  (p02 - 4 - 4 * r2),
+                              r2, P2, (P2 + 4) >> 4, ql0);
+        }
+      }
+#pragma unroll
+      for (int rr = 0; rr < GM; rr++) {
+        uint8_t *fdst =
+            dst + (stripe * (k + GM) + k + rr) * dst_stride + f * block_len;
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int q = qp + 64 * i;
+          if (FULL || q < nfull) {
+            const uint4 v = acc[rr][i];
+            if (i == 0 && q == 0) {
+              if (C0 == 0) {
+                *reinterpret_cast<u32x3a *>(fdst + 4) =
+                    u32x3a{v.y, v.z, v.w};
+              } else {
+                c0b[(k + rr) * 4 + 1] = v.y;
+                c0b[(k + rr) * 4 + 2] = v.z;
+                c0b[(k + rr) * 4 + 3] = v.w;
+              }
+            } else {
+              fstore16<ST>(fdst + 16 * q, v);
+            }
+            if (SKEL != 1) t = shift4k(t, stab) ^ crc16_reg(v, tab);
+          }
+        }
+        uint32_t part = al_mulmod(op, t);
+        if (SKEL != 1 && tail) {
+          const int p = 16 * nfull + tid;
+          if (p < T) {
+            uint8_t pv = 0;
+            for (int c2 = 0; c2 < k; c2++) {
+              const uint8_t b = tailb[c2 * 16 + tid];
+              pv ^= gfmul1_lin(ctab + size_t(rr * k + c2) * 32, b);
+            }
+            fdst[p] = pv;
+            part ^= gf2_mulmod_d(x8tab[T - 1 - p], tab[0][pv]);
+          }
+        }
+        part = al_wave_xor(part);
+        if ((tid & 63) == 0) red[(tid >> 6) * 16 + k + rr] ^= part;
+      }
+    }
+    };
+    if (P == payload_full)
+      passes(std::true_type{});
+    else
+      passes(std::false_type{});
+
+    __syncthreads();
+    { /* one frame-header lane per shard (j < k+GM <= 16, all in wave 0) */
+      const int j = tid;
+      if (j < k + GM) {
+        const uint32_t it =
+            P == payload_full
+                ? it_full
+                : gf2_mulmod_d(x8n_d(uint64_t(P)), 0xFFFFFFFFu);
+        const uint32_t crc =
+            ~(it ^ red[j] ^ red[16 + j] ^ red[32 + j] ^ red[48 + j]);
+        uint8_t *fb0 =
+            dst + (stripe * (k + GM) + j) * dst_stride + f * block_len;
+        if (C0 == 1 && nfull > 0)
+          *reinterpret_cast<uint4 *>(fb0) =
+              uint4{crc, c0b[j * 4 + 1], c0b[j * 4 + 2], c0b[j * 4 + 3]};
+        else
+          *reinterpret_cast<uint32_t *>(fb0) = crc;
+      }
+    }
+    if (tiny_len && f == frames_per_shard - 1) {
+      /* folded tiny last frame, as in rs_encode_frame_reg_k */
+      const int j = tid;
+      const int64_t tp0 = (f + 1) * payload_full;
+      if (j < k) {
+        const uint8_t *sp = sbase + size_t(j) * shard_len + tp0;
+        for (int b = 0; b < tiny_len; b++) tinyb[j * 64 + b] = sp[b];
+      }
+      __syncthreads();
+      if (j < k + GM) {
+        uint8_t *tb2 =
+            dst + (stripe * (k + GM) + j) * dst_stride + (f + 1) * block_len;
+        uint32_t cr = 0;
+        for (int b = 0; b < tiny_len; b++) {
+          uint8_t x;
+          if (j < k) {
+            x = tinyb[j * 64 + b];
+          } else {
+            x = 0;
+            for (int c2 = 0; c2 < k; c2++)
+              x ^= gfmul1_lin(ctab + size_t((j - k) * k + c2) * 32,
+                              tinyb[c2 * 64 + b]);
+          }
+          tb2[CRC_LEN + b] = x;
+          cr = tab[0][(cr ^ x) & 0xFF] ^ (cr >> 8);
+        }
+        *reinterpret_cast<uint32_t *>(tb2) =
+            ~(gf2_mulmod_d(x8n_d(uint64_t(tiny_len)), 0xFFFFFFFFu) ^ cr);
+      }
+    }
+    __syncthreads();
+    stripe = stripe2;
+    f = f2;
+  }
+}
+
+
+/* ------------------------------------------------------------------ */
 /* dual-aligned fused encode+frame: 32-B lane pieces, window rotation   */
 /* ------------------------------------------------------------------ */
 
@@ -3656,6 +4086,11 @@ void launch_rs_encode_frame_small(uint8_t *dst, size_t dst_stride,
 #undef GFRS_SM_GO
 }
 
+/* auto policy for eligible >= 1 MiB launches: the aligned kernel (79)
+ * instead of the register-CRC pipeline (76) - 29.0 vs 30.9 ms on the
+ * headline shape, profiles/r03_aligned_frame.txt */
+constexpr bool kAlAuto = true;
+
 void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
                             uint64_t stripe_stride, size_t shard_len, int k,
                             int m, const uint8_t *tabs, int nstripes,
@@ -3683,7 +4118,7 @@ void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
     switch (v) {
       case 13: case 14: case 23: case 24:
       case 72: case 73:
-      case 74: case 75: case 76: case 77: case 78:
+      case 74: case 75: case 76: case 77: case 78: case 79:
       case 86: case 87: case 96: case 97:
       case 103: case 104: case 113: case 114:
       case 142: case 152: case 162: return v;
@@ -3692,11 +4127,50 @@ void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
   }();
   /* auto policy (measured r02): >= 1 MiB shards run the 3-wave
    * register-CRC pipeline (76) whose PMC traffic is algorithmic-exact at
-   * the HBM-bound operating point; smaller shards run the 4-wave
+   * the HBM-bound operating point - or, where the layout is 16-B aligned
+   * throughout, its aligned sibling (79); smaller shards run the 4-wave
    * nontemporal form (87), whose extra latency hiding is worth more than
    * its ~10% L2-thrash traffic there (64 KiB: 1010 vs 910 GiB/s) */
-  const int var =
-      var_env >= 0 ? var_env : (shard_len >= (size_t(1) << 20) ? 76 : 87);
+  const int var_old = shard_len >= (size_t(1) << 20) ? 76 : 87;
+  /* 79 = aligned destination-space kernel (rs_encode_frame_al_k, 3 waves,
+   * plain stores).  Eligible only when every address the kernel forms is a
+   * multiple of 16; any other launch goes where it went before. */
+  const bool al_ok = ((uint64_t(reinterpret_cast<uintptr_t>(dst)) |
+                       uint64_t(dst_stride) | base | stripe_stride |
+                       uint64_t(shard_len)) & 15) == 0;
+  const int var = var_env == 79 ? (al_ok ? 79 : var_old)
+                  : var_env >= 0 ? var_env
+                  : (kAlAuto && al_ok && var_old == 76) ? 79
+                                                        : var_old;
+  if (var == 79) {
+    const int lds = 12288 + EF_RED + 64 + 256 + 1024 + 256 + m * k * 32;
+#define GFRS_AL_GO(G, SK, C)                                              \
+  hipLaunchKernelGGL((rs_encode_frame_al_k<G, 3, SK, 0, C>), dim3(grid2), \
+                     dim3(CRC_BLOCKT), lds, s, dst, dst_stride, base,     \
+                     stripe_stride, shard_len, k, ltabs, total2, fps2,    \
+                     tinyi)
+    /* diagnostics (GM=3 only): GFRS_EF_ABL=4 = memory skeleton (loads,
+     * rotation, stores; MAC and CRC compiled out), GFRS_EF_C0=1 = chunk 0
+     * held in LDS and written as one aligned uint4 in the epilogue */
+    static const int al_abl = []() {
+      const char *e = getenv("GFRS_EF_ABL");
+      return e ? atoi(e) : 0;
+    }();
+    static const int al_c0 = []() {
+      const char *e = getenv("GFRS_EF_C0");
+      return e ? atoi(e) : 0;
+    }();
+    if (m == 3 && var_env == 79 && al_abl == 4) { GFRS_AL_GO(3, 1, 0); return; }
+    if (m == 3 && var_env == 79 && al_c0 == 1) { GFRS_AL_GO(3, 0, 1); return; }
+    switch (m) {
+      case 1: GFRS_AL_GO(1, 0, 0); break;
+      case 2: GFRS_AL_GO(2, 0, 0); break;
+      case 3: GFRS_AL_GO(3, 0, 0); break;
+      default: GFRS_AL_GO(4, 0, 0);
+    }
+#undef GFRS_AL_GO
+    return;
+  }
   /* 1xy = dual-aligned 32-B-piece rotation kernel: 103/104 plain stores
    * @3/4 waves, 113/114 nontemporal @3/4 waves */
   if (var == 103 || var == 104 || var == 113 || var == 114) {
