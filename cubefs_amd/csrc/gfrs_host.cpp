@@ -236,6 +236,12 @@ struct gfrs_ctx_impl {
   DevBuf encq_buf; /* encode+frame queue: work items, frame prefix sums of
                       one call */
   PinBuf encq_pin; /* ... and the pinned host copy it is uploaded from */
+  DevBuf readq_buf; /* read queue: descriptors, identity indices, work items,
+                       frame prefix sums of one call */
+  PinBuf readq_pin; /* ... and the pinned host copy it is uploaded from */
+  DevBuf read_scratch; /* read queue, slow jobs: one decoded stripe of the
+                          touched frames; grown on demand, freed with the
+                          context */
 
   /* finalize-pipeline resources (repair path): shard_finalize of chunk i
    * runs on aux_stream behind an event while chunk i+1's repair kernel
@@ -1655,6 +1661,182 @@ int gfrs_encode_frame_queue(gfrs_ctx *ctx, void *framed, void *base,
   if (rc != GFRS_OK) return rc;
   if (e != hipSuccess) return hip_fail("encode_frame_queue launch", e);
   if (se != hipSuccess) return hip_fail("encode_frame_queue sync", se);
+  return GFRS_OK;
+}
+
+/* The read queue: crc32block decode + ReconstructData of a segment per job,
+ * as one call.  gfrs_plan.cpp validates and classes the patterns and builds
+ * the schedule; this function finds or builds the plans of the fused
+ * patterns (namespace 64), uploads one blob [npat + n descriptors | identity
+ * indices | work items | frame prefix sums], issues the <= 5 buckets, then
+ * the slow jobs one at a time, and syncs once.  Words of fused jobs come
+ * from the kernel; a slow job's word is assembled from the bad-block answers
+ * of its inputs' decodes, which sit behind the words in fail_buf. */
+int gfrs_read_queue(gfrs_ctx *ctx, void *out, const void *framed,
+                    const gfrs_gjob *jobs, int njobs, const int32_t *bad_idx,
+                    const int32_t *bad_off, int npat, int64_t block_len,
+                    uint32_t *bad_shards) {
+  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+  const Code &cd = c->code;
+  const int n = cd.t.n, nm = cd.t.n + cd.t.m;
+  int rc = read_queue_gate(cd, block_len);
+  if (rc != GFRS_OK) return rc;
+  if (njobs <= 0 || npat <= 0 || !jobs || !bad_shards)
+    return GFRS_ERR_INVALID_SHARDS;
+  if ((rc = queue_offsets_check(bad_off, npat)) != GFRS_OK) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+
+  /* every pattern, used or not: validate and class it; its inputs are the
+   * first n present of the n+m; fused rebuilds find or build their plan */
+  std::vector<ReadPattern> pats(npat);
+  std::vector<DevPlan *> plans(npat, nullptr);
+  std::vector<std::vector<uint8_t>> present(npat);
+  std::vector<uint32_t> pass(npat, 0);
+  for (int p = 0; p < npat; p++) {
+    const int32_t *bad = bad_idx + bad_off[p];
+    const int nbad = bad_off[p + 1] - bad_off[p];
+    if ((rc = read_pattern_check(cd, bad, nbad, &pats[p])) != GFRS_OK)
+      return rc;
+    present[p].assign(nm, 1);
+    PlanKey key = plan_key_tag(64);
+    for (int i = 0; i < nbad; i++)
+      if (bad[i] < nm) {
+        present[p][bad[i]] = 0;
+        plan_key_set(key, bad[i]);
+      }
+    for (int i = 0, ci = 0; i < nm && ci < n; i++)
+      if (present[p][i]) {
+        if (i < n) pass[p] |= 1u << ci;
+        ci++;
+      }
+    if (pats[p].cls != GFRS_GPAT_FUSED || pats[p].r == 0) continue;
+    auto build = [&](Plan *pl) { return plan_read(cd, bad, nbad, pl); };
+    rc = cached_plan(c, c->dec_cache, key, c->stream, std::ref(build),
+                     &plans[p]);
+    if (rc != GFRS_OK) return rc;
+  }
+  ReadSchedule sched;
+  rc = read_schedule(cd, jobs, njobs, pats.data(), npat, (uint64_t)out,
+                     &sched);
+  if (rc != GFRS_OK) return rc;
+
+  /* the slow jobs share one scratch stripe, sized for the largest */
+  const int nslow = int(sched.slow_jobs.size());
+  size_t scratch = 0;
+  for (int32_t j : sched.slow_jobs) {
+    const uint64_t raw0 = read_first_frame(jobs[j]) * REPAIR_PAYLOAD;
+    const uint64_t raw1 = std::min<uint64_t>(
+        (read_last_frame(jobs[j]) + 1) * REPAIR_PAYLOAD, jobs[j].shard_len);
+    scratch = std::max(scratch, size_t(nm) * size_t(raw1 - raw0));
+  }
+  if (scratch && (rc = c->read_scratch.ensure(scratch)) != GFRS_OK) return rc;
+
+  /* ONE blob; identity descriptors and R = 0 patterns point into it */
+  const int ndesc = npat + n;
+  const size_t o_ident = size_t(ndesc) * sizeof(ReadDesc);
+  const size_t o_items = (o_ident + size_t(n) * 4 + 15) / 16 * 16;
+  const size_t o_prefix = o_items + sched.items.size() * sizeof(gfrs_gitem);
+  const size_t nbytes = o_prefix + sched.frame_prefix.size() * 8;
+  if ((rc = c->readq_buf.ensure(nbytes)) != GFRS_OK) return rc;
+  if ((rc = c->readq_pin.ensure(nbytes)) != GFRS_OK) return rc;
+  const uint8_t *dq = (const uint8_t *)c->readq_buf.p;
+  const int32_t *d_ident = (const int32_t *)(dq + o_ident);
+  uint8_t *blob = (uint8_t *)c->readq_pin.p;
+  memset(blob, 0, o_items);
+  for (int p = 0; p < npat; p++) {
+    if (pats[p].cls != GFRS_GPAT_FUSED) continue;
+    const ReadDesc d =
+        plans[p] ? ReadDesc{plans[p]->in(), plans[p]->out(), plans[p]->tab(),
+                            plans[p]->k, pass[p]}
+                 : ReadDesc{d_ident, nullptr, nullptr, n, pass[p]};
+    memcpy(blob + size_t(p) * sizeof(ReadDesc), &d, sizeof(d));
+  }
+  for (int s = 0; s < n; s++) {
+    const ReadDesc d{d_ident + s, nullptr, nullptr, 1, 1u};
+    memcpy(blob + size_t(npat + s) * sizeof(ReadDesc), &d, sizeof(d));
+    const int32_t idx = s;
+    memcpy(blob + o_ident + size_t(s) * 4, &idx, 4);
+  }
+  if (!sched.items.empty()) {
+    memcpy(blob + o_items, sched.items.data(), o_prefix - o_items);
+    memcpy(blob + o_prefix, sched.frame_prefix.data(), nbytes - o_prefix);
+  }
+
+  /* fail_buf: njobs words, then one bad-block answer per slow-job input */
+  const size_t o_bad = (size_t(njobs) * 4 + 7) / 8 * 8;
+  const size_t nfail = o_bad + size_t(nslow) * n * 8;
+  if ((rc = c->fail_buf.ensure(nfail)) != GFRS_OK) return rc;
+  uint32_t *fail = (uint32_t *)c->fail_buf.p;
+  int64_t *dbad = (int64_t *)((uint8_t *)c->fail_buf.p + o_bad);
+  hipError_t e = hipMemsetAsync(fail, 0, o_bad, c->stream);
+  if (e == hipSuccess && nslow)
+    e = hipMemsetAsync(dbad, 0xFF, nfail - o_bad, c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->readq_buf.p, blob, nbytes, hipMemcpyHostToDevice,
+                       c->stream);
+  if (e == hipSuccess) {
+    for (const ReadBucket &b : sched.buckets)
+      launch_rs_read_frame_queue(
+          (uint8_t *)out, (uint64_t)framed,
+          (const gfrs_gitem *)(dq + o_items) + b.first,
+          (const uint64_t *)(dq + o_prefix) + b.prefix, uint32_t(b.count),
+          sched.frame_prefix[b.prefix + b.count], (const ReadDesc *)dq, n, b.r,
+          fail, c->stream);
+    e = hipGetLastError();
+  }
+  /* slow jobs: decode the touched frames of the inputs into the scratch
+   * stripe, rebuild the missing data there, copy the segment out */
+  std::vector<int32_t> gidx(nm);
+  for (int i = 0; i < nm; i++) gidx[i] = i;
+  const Engine ge{n, cd.t.m, cd.enc_matrix.data(), gidx.data()};
+  for (int q = 0; q < nslow && rc == GFRS_OK && e == hipSuccess; q++) {
+    const gfrs_gjob &jb = jobs[sched.slow_jobs[q]];
+    const uint64_t f0 = read_first_frame(jb), f1 = read_last_frame(jb);
+    const uint64_t raw0 = f0 * REPAIR_PAYLOAD;
+    const uint64_t flen =
+        std::min<uint64_t>((f1 + 1) * REPAIR_PAYLOAD, jb.shard_len) - raw0;
+    uint8_t *sc = (uint8_t *)c->read_scratch.p;
+    const std::vector<uint8_t> &pr = present[jb.pattern];
+    for (int i = 0, ci = 0; i < nm && ci < n; i++) {
+      if (!pr[i]) continue;
+      launch_crc_decode(sc + size_t(i) * flen, 0,
+                        (const uint8_t *)framed + jb.img_off +
+                            size_t(i) * jb.img_stride + f0 * REPAIR_BLOCK,
+                        0, int64_t(flen + 4 * (f1 - f0 + 1)), REPAIR_BLOCK, 1,
+                        dbad + size_t(q) * n + ci, c->stream);
+      ci++;
+    }
+    rc = reconstruct_engine(c, view_of(c), ge, pr, flen, 1, /*data_only=*/1,
+                            strided(sc, 0), /*tag=*/1);
+    if (rc == GFRS_OK)
+      e = hipMemcpy2DAsync((uint8_t *)out + jb.out_off, jb.out_stride,
+                           sc + (jb.seg_off - raw0), flen, jb.seg_len, n,
+                           hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+  }
+  std::vector<uint8_t> back(nfail);
+  if (rc == GFRS_OK && e == hipSuccess)
+    e = hipMemcpyAsync(back.data(), c->fail_buf.p, nfail,
+                       hipMemcpyDeviceToHost, c->stream);
+  hipError_t se = hipStreamSynchronize(c->stream); /* the one sync; the blob
+                                                      is read until here */
+  if (rc != GFRS_OK) return rc;
+  if (e != hipSuccess) return hip_fail("read_queue launch", e);
+  if (se != hipSuccess) return hip_fail("read_queue sync", se);
+  memcpy(bad_shards, back.data(), size_t(njobs) * 4);
+  for (int q = 0; q < nslow; q++) {
+    const std::vector<uint8_t> &pr = present[jobs[sched.slow_jobs[q]].pattern];
+    uint32_t word = 0;
+    for (int i = 0, ci = 0; i < nm && ci < n; i++) {
+      if (!pr[i]) continue;
+      int64_t b;
+      memcpy(&b, &back[o_bad + (size_t(q) * n + ci) * 8], 8);
+      if (b != -1) word |= 1u << i;
+      ci++;
+    }
+    bad_shards[sched.slow_jobs[q]] = word;
+  }
   return GFRS_OK;
 }
 

@@ -171,6 +171,34 @@ void launch_rs_repair_frame_queue(uint8_t *dst, uint64_t base,
 void launch_shard_finalize_queue(uint8_t *dst, const gfrs_rimage *imgs,
                                  int nimg, hipStream_t s);
 
+/* Read queue: one bucket of the read schedule (gfrs_plan.h), i.e. every work
+ * item whose descriptor rebuilds r rows (0..4).  An item reads the frames its
+ * segment touches of the images of its descriptor's k inputs,
+ *   payload of frame f of input c at
+ *     framed + item.img + imap[c] * item.img_stride + f * 65536 + 4,
+ * checks their CRCs against the stored headers, and writes the segment of
+ *   every input with its pass bit set, to row imap[c], and
+ *   the r rebuilt shards, to rows omap[0..r),
+ * row i at out + item.out + i * item.out_stride.  descs[item.desc] points
+ * into the cached DevPlans, or into the call's blob for identity descriptors;
+ * frame_prefix holds the nitems+1 exclusive prefix sums of touched frames,
+ * total_frames its last entry; kmax bounds every descriptor's k (it sizes the
+ * LDS tables, at most 16).  A CRC mismatch of input c ORs 1 << imap[c] into
+ * fail[item.job]. */
+struct ReadDesc {
+  const int32_t *imap; /* k inputs */
+  const int32_t *omap; /* r rebuilt shards */
+  const uint8_t *tabs; /* [r*k][32]; unused when r == 0 */
+  int32_t k;
+  uint32_t pass_mask; /* bit c: input c is copied to row imap[c] */
+};
+void launch_rs_read_frame_queue(uint8_t *out, uint64_t framed,
+                                const gfrs_gitem *items,
+                                const uint64_t *frame_prefix, uint32_t nitems,
+                                uint64_t total_frames, const ReadDesc *descs,
+                                int kmax, int r, uint32_t *fail,
+                                hipStream_t s);
+
 /* EncodeIdx-style accumulate apply (reedsolomon.go:631-668):
  * out[r] ^= coeff[r]*in for one input shard. */
 void launch_rs_apply_xor(const uint64_t *ptrs, int nptr,

@@ -3901,6 +3901,393 @@ void launch_rs_repair_frame_queue(uint8_t *dst, uint64_t base,
 #undef GFRS_RQ_GO
 }
 
+/* ---- read queue: verify + rebuild + unframe in one pass ---- */
+
+/* Store the 16-byte piece at frame position x (a multiple of 4) through
+ * `rowf`, the address frame position 0 of the row would have, clipped to the
+ * frame positions [lo, hi) the segment covers (lo a multiple of 4): the whole
+ * dwords inside, nothing outside.  `inside` (block-uniform) says the whole
+ * pass lies in [lo, hi).  The last dword of a segment with hi % 4 != 0 is
+ * store_clip_tail's. */
+GFRS_DEV void store_clip16(uint8_t *rowf, int x, int lo, int hi, bool inside,
+                           const uint4 v) {
+  uint32_t *dw = reinterpret_cast<uint32_t *>(rowf + x);
+  if (inside) {
+    dw[0] = v.x; dw[1] = v.y; dw[2] = v.z; dw[3] = v.w;
+  } else {
+    if (x >= lo && x + 4 <= hi) dw[0] = v.x;
+    if (x + 4 >= lo && x + 8 <= hi) dw[1] = v.y;
+    if (x + 8 >= lo && x + 12 <= hi) dw[2] = v.z;
+    if (x + 12 >= lo && x + 16 <= hi) dw[3] = v.w;
+  }
+}
+
+/* The partial last dword of the segment (hi % 4 != 0), byte by byte, when it
+ * lies in the nv = rbi & ~15 bytes of the pass at r0 that lanes hold as
+ * 16-byte pieces v[0..3] (lane l: pass offsets i * 4096 + 16 * l); in the
+ * ragged tail behind them it is the byte path's.  The test is block-uniform;
+ * one lane stores at most 3 bytes. */
+GFRS_DEV void store_clip_tail(uint8_t *rowf, int r0, int nv, int hi,
+                              const uint4 (&v)[4]) {
+  const int hq = hi & ~3, pr = hq - r0;
+  if ((hi & 3) && pr >= 0 && pr < nv &&
+      int(threadIdx.x) == ((pr & 4095) >> 4)) {
+    /* constant indices only, so that v stays in registers */
+    const int sel = pr >> 12 << 2 | (pr & 15) >> 2;
+    uint32_t w = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      if (sel == 4 * i) w = v[i].x;
+      if (sel == 4 * i + 1) w = v[i].y;
+      if (sel == 4 * i + 2) w = v[i].z;
+      if (sel == 4 * i + 3) w = v[i].w;
+    }
+#pragma unroll
+    for (int b = 0; b < 3; b++)
+      if (b < (hi & 3)) rowf[hq + b] = uint8_t(w >> (8 * b));
+  }
+}
+
+/* The read direction of the fused frame kernels (the degraded GET): frames
+ * in, raw segment out.  The walk is rs_repair_frame_queue_k's - a contiguous
+ * frame range per block, one binary search then a forward walk over the
+ * prefix sums, block-uniform descriptor restage between two barriers, scalar
+ * item loads, every pointer rebuilt from the item - but the prefix sums count
+ * the frames an item's segment TOUCHES, and frame f of the walk is frame
+ * seg_off / 65532 + f of the shard.  The data flow is inverted: for each
+ * 16 KiB pass and each input c of the descriptor a lane
+ *   1. takes its four 16-byte pieces of the input's PAYLOAD (image offset
+ *      f * 65536 + 4 + pass offset), prefetched under the previous input,
+ *   2. Horner-chains them through the register CRC (crc16_reg / shift4k) and
+ *      folds by its position operator - the operators of crc32b_verify_reg_k,
+ *   3. stores them to the input's own row when the input is a data shard,
+ *   4. MACs them into the R accumulators (R > 0),
+ * then stores the R rebuilt rows.  Every store is clipped to the segment
+ * (store_clip16: dword granular at the head, where seg_off % 4 == 0 keeps
+ * raw positions and addresses congruent; store_clip_tail: byte granular at
+ * the tail).  The CRC of input c is reduced per wave into red[wave][c];
+ * the ragged tail bytes of a frame (12 of a full frame's last pass) go
+ * through the (input, byte) lane mapping of the repair kernel's tailb stage
+ * and XOR their CRC terms into red[4][c].  At the end of a frame lane c
+ * compares input c's CRC with the stored 4-byte LE header and ORs
+ * 1 << shard into fail[item.job].
+ * Frame f of every shard of a stripe covers the same raw range, so one lane
+ * mapping serves all inputs and outputs.  No lane leaves the frame loop
+ * early; no load leaves the touched frames of the item's input images; no
+ * store leaves the item's declared rows.  There is no cross-frame prefetch:
+ * the first input of a frame is loaded at its top. */
+constexpr int RD_RED = 5 * 16 * 4; /* red[4 waves + tail][16 inputs] */
+constexpr int RD_LDS = 12288 + RD_RED + 64 + 256; /* ctab follows */
+
+template <int R, int WPS>
+__global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_read_frame_queue_k(
+    uint8_t *__restrict__ out, uint64_t framed,
+    const gfrs_gitem *__restrict__ items,
+    const uint64_t *__restrict__ frame_prefix, uint32_t nitems,
+    uint64_t total_frames, const ReadDesc *__restrict__ descs,
+    uint32_t *__restrict__ fail) {
+  constexpr int EF_PASS = 16384;
+  constexpr int EF_PASSES = 4;
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+  constexpr int RR = R > 0 ? R : 1;
+
+  const uint64_t per_blk = (total_frames + gridDim.x - 1) / gridDim.x;
+  const uint64_t f_lo = uint64_t(blockIdx.x) * per_blk;
+  const uint64_t f_hi =
+      f_lo + per_blk < total_frames ? f_lo + per_blk : total_frames;
+  if (f_lo >= f_hi) return; /* whole block, before any barrier */
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t(*tab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem);
+  uint32_t(*stab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem + 8192);
+  uint32_t *red = reinterpret_cast<uint32_t *>(smem + 12288);
+  uint32_t *x8tab = reinterpret_cast<uint32_t *>(smem + 12288 + RD_RED);
+  uint8_t *tailb = smem + 12288 + RD_RED + 64;
+  uint8_t *ctab = smem + RD_LDS;
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift4k[0][0])[i];
+  if (threadIdx.x == 0) {
+    uint32_t v = 0x80000000u;
+    for (int j = 0; j < 16; j++) {
+      x8tab[j] = v;
+      v = gf2_mulmod_d(v, g_pow8[0]);
+    }
+  }
+  const int64_t lane16 = int64_t(threadIdx.x) * 16;
+  const int lane16i = int(threadIdx.x) * 16;
+  constexpr uint32_t INV16K = 0x479933FCu;
+  const uint32_t op_pA =
+      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16 + 16)));
+  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
+  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
+  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  const uint32_t it_full =
+      gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
+  __syncthreads();
+
+  /* largest it with frame_prefix[it] <= f_lo (frame_prefix[0] == 0) */
+  uint32_t it = 0;
+  for (uint32_t hi = nitems; hi - it > 1;) {
+    const uint32_t mid = it + (hi - it) / 2;
+    if (frame_prefix[mid] <= f_lo)
+      it = mid;
+    else
+      hi = mid;
+  }
+
+  typedef const __attribute__((address_space(4))) int32_t *IdxList;
+  int cur_desc = -1;
+  IdxList imap = nullptr, omap = nullptr;
+  int k = 0;
+  uint32_t pass = 0;
+
+  for (uint64_t fr = f_lo; fr < f_hi; fr++) {
+    while (frame_prefix[it + 1] <= fr) it++; /* it + 1 <= nitems */
+    const gfrs_gitem item = items[it];
+    if (item.desc != cur_desc) {
+      const ReadDesc d = descs[item.desc];
+      if (R > 0) {
+        __syncthreads(); /* all lanes are done with the old tables */
+        const uint4 *src =
+            reinterpret_cast<const uint4 *>(as_global(uint64_t(d.tabs)));
+        for (int i = threadIdx.x; i < R * d.k * 2; i += CRC_BLOCKT)
+          reinterpret_cast<uint4 *>(ctab)[i] = src[i];
+        __syncthreads();
+      }
+      cur_desc = item.desc;
+      imap = (IdxList)(uint64_t)d.imap;
+      omap = (IdxList)(uint64_t)d.omap;
+      k = d.k;
+      pass = d.pass_mask;
+    }
+    /* frame f of the shard: the item's first touched frame + its walk index.
+     * Everything below is 32-bit and relative to the frame: payload bytes,
+     * and [lo, hi), the frame positions the segment covers (lo % 4 == 0) */
+    const int64_t f = int64_t(item.seg_off / uint64_t(payload_full)) +
+                      int64_t(fr - frame_prefix[it]);
+    const int64_t p0 = f * payload_full;
+    const int payload =
+        int(i64min(payload_full, int64_t(item.shard_len) - p0));
+    const int64_t slo = int64_t(item.seg_off) - p0;
+    const int64_t shi = slo + int64_t(item.seg_len);
+    const int lo = slo > 0 ? int(slo) : 0;
+    const int hi = shi < int64_t(payload) ? int(shi) : payload;
+    /* frame f of image 0 (image i at + i * img_stride), and the address
+     * frame position 0 of row 0 would have (row i at + i * out_stride); a row
+     * is dereferenced inside [lo, hi) only */
+    const uint8_t *ibase = as_global(framed + item.img) + f * block_len;
+    uint8_t *obase = reinterpret_cast<uint8_t *>(
+        uint64_t(out) + item.out + uint64_t(p0) - item.seg_off);
+
+    uint4 vnext[4];
+    { /* pass 0, input 0 */
+      const int rb0 = payload < EF_PASS ? payload : EF_PASS;
+      const uint8_t *src0 =
+          ibase + size_t(imap[0]) * item.img_stride + CRC_LEN;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        vnext[i] = off + 16 <= rb0
+                       ? *reinterpret_cast<const uint4 *>(src0 + off)
+                       : uint4{0, 0, 0, 0};
+      }
+    }
+    for (int j = threadIdx.x; j < RD_RED / 4; j += CRC_BLOCKT) red[j] = 0;
+    __syncthreads();
+
+#pragma unroll 1
+    for (int h = 0; h < EF_PASSES; h++) {
+      const int r0 = h * EF_PASS;
+      const int rbi = payload - r0 < EF_PASS ? payload - r0 : EF_PASS;
+      if (rbi <= 0) break; /* block-uniform */
+      const int rbn =
+          payload - r0 - EF_PASS < EF_PASS ? payload - r0 - EF_PASS : EF_PASS;
+      const bool inside = lo <= r0 && r0 + rbi <= hi; /* block-uniform */
+
+      uint4 acc[RR][4];
+#pragma unroll
+      for (int r = 0; r < RR; r++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[r][i] = uint4{0, 0, 0, 0};
+
+      uint32_t op = h == 0   ? op_pA
+                    : h == 1 ? op_pB
+                    : h == 2 ? op_pC
+                             : op_pD;
+      if (h == EF_PASSES - 1 && threadIdx.x == 255)
+        op = shift4k(op, stab); /* lane 255's last pass has 3 pieces */
+      if (payload != int(payload_full)) {
+        int np = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (i * 4096 + lane16i + 16 <= rbi) np = i + 1;
+        const int end = np ? r0 + (np - 1) * 4096 + lane16i + 16 : r0;
+        op = x8n_d(uint64_t(payload - end));
+      }
+
+      for (int c = 0; c < k; c++) {
+        uint4 vcur[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) vcur[i] = vnext[i];
+        { /* the next input's loads, or the next pass's first input's, fly
+             over this input's CRC and MAC */
+          const bool more = c + 1 < k;
+          const int nb = more ? rbi : rbn;
+          const uint8_t *nsrc =
+              ibase + size_t(imap[more ? c + 1 : 0]) * item.img_stride +
+              CRC_LEN + r0 + (more ? 0 : EF_PASS);
+          if (nb > 0) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+              const int off = i * 4096 + lane16i;
+              vnext[i] = off + 16 <= nb
+                             ? *reinterpret_cast<const uint4 *>(nsrc + off)
+                             : uint4{0, 0, 0, 0};
+            }
+          }
+        }
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int off = i * 4096 + lane16i;
+          if (off + 16 <= rbi) t = shift4k(t, stab) ^ crc16_reg(vcur[i], tab);
+        }
+        uint32_t part = t ? gf2_mulmod_d(op, t) : 0;
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) part ^= __shfl_xor(part, sh, 64);
+        if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * 16 + c] ^= part;
+
+        if ((pass >> c) & 1) { /* a surviving data shard: its own row */
+          uint8_t *rowf = obase + size_t(imap[c]) * item.out_stride;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            if (off + 16 <= rbi)
+              store_clip16(rowf, r0 + off, lo, hi, inside, vcur[i]);
+          }
+          if (!inside) store_clip_tail(rowf, r0, rbi & ~15, hi, vcur);
+        }
+        if (R > 0) {
+          LinTab lt[RR];
+#pragma unroll
+          for (int r = 0; r < RR; r++) lt[r] = lintab_load(ctab, r * k + c);
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            if (off + 16 <= rbi) {
+#pragma unroll
+              for (int d = 0; d < 4; d++)
+                gfmac4_lin_rows<RR>(acc, i, d, (&vcur[i].x)[d], lt);
+            }
+          }
+        }
+      }
+      if (R > 0) { /* the rebuilt rows */
+#pragma unroll
+        for (int r = 0; r < RR; r++) {
+          uint8_t *rowf = obase + size_t(omap[r]) * item.out_stride;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            if (off + 16 <= rbi)
+              store_clip16(rowf, r0 + off, lo, hi, inside, acc[r][i]);
+          }
+          if (!inside) store_clip_tail(rowf, r0, rbi & ~15, hi, acc[r]);
+        }
+      }
+      if (rbi & 15) { /* ragged tail of the frame: lane (input c2, byte j) */
+        const int tt0 = rbi & ~15;
+        const int c2 = int(threadIdx.x) >> 4, j = int(threadIdx.x) & 15;
+        if (c2 < k && tt0 + j < rbi) {
+          const int sh = imap[c2];
+          const uint8_t x =
+              ibase[size_t(sh) * item.img_stride + CRC_LEN + r0 + tt0 + j];
+          tailb[c2 * 16 + j] = x;
+          atomicXor(&red[64 + c2],
+                    gf2_mulmod_d(x8tab[rbi - 1 - (tt0 + j)], tab[0][x]));
+          const int q = r0 + tt0 + j;
+          if (((pass >> c2) & 1) && q >= lo && q < hi)
+            obase[size_t(sh) * item.out_stride + q] = x;
+        }
+        if (R > 0) {
+          __syncthreads(); /* block-uniform: rbi is */
+          const int p = tt0 + int(threadIdx.x);
+          const int q = r0 + p;
+          if (p < rbi && q >= lo && q < hi) {
+#pragma unroll
+            for (int r = 0; r < RR; r++) {
+              uint8_t pv = 0;
+              for (int c3 = 0; c3 < k; c3++)
+                pv ^= gfmul1_lin(ctab + size_t(r * k + c3) * 32,
+                                 tailb[c3 * 16 + (p - tt0)]);
+              obase[size_t(omap[r]) * item.out_stride + q] = pv;
+            }
+          }
+        }
+      }
+    }
+
+    __syncthreads();
+    if (int(threadIdx.x) < k) { /* lane c: input c's CRC against its header */
+      const int c = int(threadIdx.x);
+      const int sh = imap[c];
+      const uint32_t itv =
+          payload == int(payload_full)
+              ? it_full
+              : gf2_mulmod_d(x8n_d(uint64_t(payload)), 0xFFFFFFFFu);
+      const uint32_t crc = ~(itv ^ red[c] ^ red[16 + c] ^ red[32 + c] ^
+                             red[48 + c] ^ red[64 + c]);
+      const uint8_t *hp = ibase + size_t(sh) * item.img_stride;
+      const uint32_t want = uint32_t(hp[0]) | (uint32_t(hp[1]) << 8) |
+                            (uint32_t(hp[2]) << 16) | (uint32_t(hp[3]) << 24);
+      if (want != crc) atomicOr(&fail[item.job], 1u << sh);
+    }
+    __syncthreads();
+  }
+}
+
+void launch_rs_read_frame_queue(uint8_t *out, uint64_t framed,
+                                const gfrs_gitem *items,
+                                const uint64_t *frame_prefix, uint32_t nitems,
+                                uint64_t total_frames, const ReadDesc *descs,
+                                int kmax, int r, uint32_t *fail,
+                                hipStream_t s) {
+  if (nitems == 0 || total_frames == 0) return;
+  /* the cap of the other frame queues, read on every launch: GFRS_CRC_GRID
+   * forces the multi-frame walk and the restage at tiny shapes */
+  const uint64_t cap = uint64_t(env_grid("GFRS_CRC_GRID", 16384));
+  const int grid = int(total_frames < cap ? total_frames : cap);
+  const int lds = RD_LDS + r * kmax * 32;
+  /* waves per SIMD: 4 for R = 0; 3 for R >= 1 - measured for R = 1 (1 % ahead
+   * of 4 on 128 x 4 MiB), and the only build without spills for R >= 2
+   * (DESIGN.md, section 15).  GFRS_RD_WAVES = 3 or 4 overrides it; like
+   * GFRS_CRC_GRID it is read on every launch, so a test can run both builds
+   * of every R. */
+  const char *we = getenv("GFRS_RD_WAVES");
+  const int wv = we ? atoi(we) : 0;
+#define GFRS_RD_GO(G, W)                                                   \
+  hipLaunchKernelGGL((rs_read_frame_queue_k<G, W>), dim3(grid),            \
+                     dim3(CRC_BLOCKT), lds, s, out, framed, items,         \
+                     frame_prefix, nitems, total_frames, descs, fail)
+#define GFRS_RD_SEL(G, DFLT)                                               \
+  do {                                                                     \
+    if ((wv == 3 || wv == 4 ? wv : DFLT) == 3) GFRS_RD_GO(G, 3);           \
+    else GFRS_RD_GO(G, 4);                                                 \
+  } while (0)
+  switch (r) {
+    case 0: GFRS_RD_SEL(0, 4); break;
+    case 1: GFRS_RD_SEL(1, 3); break;
+    case 2: GFRS_RD_SEL(2, 3); break;
+    case 3: GFRS_RD_SEL(3, 3); break;
+    default: GFRS_RD_SEL(4, 3);
+  }
+#undef GFRS_RD_SEL
+#undef GFRS_RD_GO
+}
+
 /* Small-shard fused encode+frame: one 64-lane WAVE per stripe, no LDS
  * staging, no barriers (everything wave-local).  Shard <= 4096 B is one
  * short crc32block frame; lane w owns pieces {i*1024 + 16w : i < NI}

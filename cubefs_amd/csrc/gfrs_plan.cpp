@@ -622,9 +622,181 @@ int encode_queue_schedule(const gfrs_ejob *jobs, int njobs,
   return GFRS_OK;
 }
 
+/* ---- the read queue ---- */
+
+int plan_read(const Code &c, const int32_t *bad, int nbad, Plan *p) {
+  const int k = c.t.n, m = c.t.m;
+  std::vector<uint8_t> present(k + m, 1);
+  for (int i = 0; i < nbad; i++) {
+    if (bad[i] < 0 || bad[i] >= c.total) return GFRS_ERR_INVALID_SHARDS;
+    if (bad[i] < k + m) present[bad[i]] = 0; /* local parities: ignored */
+  }
+  std::vector<int32_t> gidx(k + m);
+  for (int i = 0; i < k + m; i++) gidx[i] = i;
+  const Engine g{k, m, c.enc_matrix.data(), gidx.data()};
+  int rc = plan_decode(g, present.data(), p);
+  if (rc != GFRS_OK) return rc;
+  for (size_t ci = 0; ci < p->in.size() && ci < 32; ci++)
+    if (p->in[ci] < k) p->pass_mask |= 1u << ci;
+  return GFRS_OK;
+}
+
+int read_pattern_check(const Code &c, const int32_t *bad, int nbad,
+                       ReadPattern *r) {
+  *r = ReadPattern();
+  if (nbad < 0 || (nbad > 0 && !bad)) return GFRS_ERR_INVALID_SHARDS;
+  std::vector<uint8_t> seen(c.total, 0);
+  int nglobal = 0, ndata = 0;
+  for (int i = 0; i < nbad; i++) {
+    if (bad[i] < 0 || bad[i] >= c.total || seen[bad[i]])
+      return GFRS_ERR_INVALID_SHARDS;
+    seen[bad[i]] = 1;
+    nglobal += bad[i] < c.t.n + c.t.m;
+    ndata += bad[i] < c.t.n;
+  }
+  if (nglobal > c.t.m) return GFRS_ERR_TOO_FEW_SHARDS;
+  r->r = ndata;
+  if (c.total <= 16)
+    r->cls = ndata <= READ_ROWS ? GFRS_GPAT_FUSED : GFRS_GPAT_SLOW;
+  else
+    r->cls = ndata == 0 ? GFRS_GPAT_IDENTITY : GFRS_GPAT_SLOW;
+  return GFRS_OK;
+}
+
+int read_pattern(const Code &c, const int32_t *bad, int nbad, Plan *p,
+                 ReadPattern *r) {
+  int rc = read_pattern_check(c, bad, nbad, r);
+  if (rc != GFRS_OK) return rc;
+  return plan_read(c, bad, nbad, p);
+}
+
+int read_queue_gate(const Code &c, int64_t block_len) {
+  int rc = encode_queue_block_check(block_len);
+  if (rc != GFRS_OK) return rc;
+  return c.t.n + c.t.m <= READ_WORD_BITS ? GFRS_OK : GFRS_ERR_UNSUPPORTED;
+}
+
+int read_schedule(const Code &c, const gfrs_gjob *jobs, int njobs,
+                  const ReadPattern *pats, int npat, uint64_t out_addr,
+                  ReadSchedule *out) {
+  *out = ReadSchedule();
+  if (njobs <= 0 || npat <= 0 || !jobs || !pats) return GFRS_ERR_INVALID_SHARDS;
+  const int n = c.t.n;
+  size_t count[READ_ROWS + 1] = {0};
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_gjob &jb = jobs[j];
+    if (jb.pattern < 0 || jb.pattern >= npat || jb.reserved != 0)
+      return GFRS_ERR_INVALID_SHARDS;
+    if (jb.shard_len == 0 || jb.seg_len == 0) return GFRS_ERR_SHARD_NO_DATA;
+    if (jb.seg_off % 4 || (out_addr + jb.out_off) % 4 || jb.out_stride % 4)
+      return GFRS_ERR_INVALID_SHARDS;
+    if (jb.out_stride < jb.seg_len ||
+        jb.img_stride < encode_image_size(jb.shard_len) ||
+        jb.seg_off > jb.shard_len || jb.seg_len > jb.shard_len - jb.seg_off)
+      return GFRS_ERR_INVALID_SHARDS;
+    const ReadPattern &rp = pats[jb.pattern];
+    if (rp.cls == GFRS_GPAT_FUSED)
+      count[rp.r]++;
+    else if (rp.cls == GFRS_GPAT_IDENTITY)
+      count[0] += size_t(n);
+  }
+  size_t bucket_of[READ_ROWS + 1], nitems = 0;
+  for (int r = 0; r <= READ_ROWS; r++) {
+    if (!count[r]) continue;
+    ReadBucket b;
+    b.r = r;
+    b.first = nitems;
+    b.count = count[r];
+    b.prefix = nitems + out->buckets.size();
+    bucket_of[r] = out->buckets.size();
+    nitems += count[r];
+    out->buckets.push_back(b);
+  }
+  out->items.reserve(nitems);
+  /* caller order first; a stable sort by descriptor then leaves the items of
+   * one descriptor in caller order */
+  std::vector<std::vector<gfrs_gitem>> per(READ_ROWS + 1);
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_gjob &jb = jobs[j];
+    const ReadPattern &rp = pats[jb.pattern];
+    gfrs_gitem it{jb.img_off, jb.img_stride, jb.shard_len, jb.seg_off,
+                  jb.seg_len, jb.out_off,    jb.out_stride, j, jb.pattern};
+    if (rp.cls == GFRS_GPAT_FUSED) {
+      per[rp.r].push_back(it);
+    } else if (rp.cls == GFRS_GPAT_IDENTITY) {
+      for (int s = 0; s < n; s++) {
+        it.desc = npat + s;
+        per[0].push_back(it);
+      }
+    } else {
+      out->slow_jobs.push_back(j);
+    }
+  }
+  out->frame_prefix.assign(nitems + out->buckets.size(), 0);
+  for (int r = 0; r <= READ_ROWS; r++) {
+    if (!count[r]) continue;
+    std::stable_sort(per[r].begin(), per[r].end(),
+                     [](const gfrs_gitem &a, const gfrs_gitem &b) {
+                       return a.desc < b.desc;
+                     });
+    const ReadBucket &bk = out->buckets[bucket_of[r]];
+    for (size_t i = 0; i < per[r].size(); i++) {
+      const gfrs_gitem &it = per[r][i];
+      out->items.push_back(it);
+      out->frame_prefix[bk.prefix + i + 1] =
+          out->frame_prefix[bk.prefix + i] +
+          (it.seg_off + it.seg_len - 1) / REPAIR_PAYLOAD -
+          it.seg_off / REPAIR_PAYLOAD + 1;
+    }
+  }
+  return GFRS_OK;
+}
+
 }  // namespace gfrs
 
 /* ---- GPU-free diagnostic export (include/gfrs.h) ---- */
+
+extern "C" int gfrs_compute_read_queue_schedule(
+    const gfrs_tactic *t, const gfrs_gjob *jobs, int njobs,
+    const int32_t *bad_idx, const int32_t *bad_off, int npat,
+    int64_t block_len, int item_cap, gfrs_gitem *items,
+    uint64_t *frame_prefix, int *nitems, gfrs_gbucket *buckets, int *nbuckets,
+    int32_t *pat_class, int32_t *pat_r, int32_t *slow_jobs, int *nslow) {
+  using namespace gfrs;
+  if (!tactic_valid(t) || t->m == 0) return GFRS_ERR_INVALID_CODEMODE;
+  Code c;
+  if (!code_build(*t, &c)) return GFRS_ERR_SINGULAR;
+  int rc = read_queue_gate(c, block_len);
+  if (rc != GFRS_OK) return rc;
+  if (njobs <= 0 || npat <= 0) return GFRS_ERR_INVALID_SHARDS;
+  if ((rc = queue_offsets_check(bad_off, npat)) != GFRS_OK) return rc;
+  std::vector<ReadPattern> pats(npat);
+  for (int p = 0; p < npat; p++) {
+    Plan pl;
+    rc = read_pattern(c, bad_idx + bad_off[p], bad_off[p + 1] - bad_off[p],
+                      &pl, &pats[p]);
+    if (rc != GFRS_OK) return rc;
+  }
+  ReadSchedule s;
+  if ((rc = read_schedule(c, jobs, njobs, pats.data(), npat, 0, &s)) != GFRS_OK)
+    return rc;
+  if (s.items.size() > size_t(item_cap < 0 ? 0 : item_cap))
+    return GFRS_ERR_NOMEM;
+  *nitems = int(s.items.size());
+  *nbuckets = int(s.buckets.size());
+  *nslow = int(s.slow_jobs.size());
+  std::copy(s.items.begin(), s.items.end(), items);
+  std::copy(s.frame_prefix.begin(), s.frame_prefix.end(), frame_prefix);
+  for (size_t b = 0; b < s.buckets.size(); b++)
+    buckets[b] = gfrs_gbucket{s.buckets[b].r, int32_t(s.buckets[b].first),
+                              int32_t(s.buckets[b].count), 0};
+  for (int p = 0; p < npat; p++) {
+    pat_class[p] = pats[p].cls;
+    pat_r[p] = pats[p].r;
+  }
+  std::copy(s.slow_jobs.begin(), s.slow_jobs.end(), slow_jobs);
+  return GFRS_OK;
+}
 
 extern "C" int gfrs_compute_encode_queue_schedule(
     const gfrs_tactic *t, const gfrs_ejob *jobs, int njobs, int64_t block_len,
@@ -762,6 +934,11 @@ extern "C" int gfrs_compute_plan(const gfrs_tactic *t, int kind,
   if (kind == GFRS_PLAN_LRC_RECONSTRUCT_VERIFY)
     rc = plan_lrc_reconstruct_verify(c, bad, nbad, &p);
   if (kind == GFRS_PLAN_FUSED_REPAIR) rc = plan_fused_repair(c, bad, nbad, &p);
+  if (kind == GFRS_PLAN_READ) {
+    ReadPattern rp;
+    rc = read_pattern(c, bad, nbad, &p, &rp);
+    p.colpack = p.pass_mask;
+  }
   if (rc != GFRS_OK) return rc;
   if (int(p.in.size()) > cap || int(p.out.size()) > cap) return GFRS_ERR_NOMEM;
   *nin = int(p.in.size());

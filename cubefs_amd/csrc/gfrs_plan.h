@@ -78,6 +78,8 @@ struct Plan {
   uint32_t cmp_mask = 0;
   uint32_t colpack = 0; /* fused repair: nibble r = caller's image column
                            of the r-th rebuild row */
+  uint32_t pass_mask = 0; /* read plan: bit c = in[c] is a data shard, which
+                             the read kernel passes through to row in[c] */
 };
 
 /* Every builder returns GFRS_OK or an error code and leaves *p complete.
@@ -271,6 +273,74 @@ int encode_queue_block_check(int64_t block_len);
  * of framed, for the alignment rule) and the schedule. */
 int encode_queue_schedule(const gfrs_ejob *jobs, int njobs,
                           uint64_t framed_addr, EncSchedule *out);
+
+/* ---- the read queue (gfrs_read_queue) ----
+ * The degraded GET: crc32block decode of the surviving images and
+ * ReconstructData of a segment, in one pass over the images.  A pattern is
+ * classed by R, its number of missing data shards:
+ *   FUSED     R <= READ_ROWS and total <= 16: a job is one work item of the
+ *             pattern's plan_read descriptor in the bucket of its R;
+ *   IDENTITY  R == 0 on a wider tactic: a job is one item per data shard s
+ *             under the identity descriptor npat + s (k = 1, one pass-through
+ *             input), in the R = 0 bucket;
+ *   SLOW      everything else: one job at a time on the host's slow path.
+ * So the fused launches number at most READ_ROWS + 1 whatever the queue. */
+constexpr int READ_ROWS = 4; /* rebuilt rows of the read kernel */
+constexpr int READ_WORD_BITS = 32; /* shards a verdict word can name */
+
+struct ReadPattern {
+  int cls = GFRS_GPAT_FUSED;
+  int r = 0; /* missing data shards */
+};
+
+/* the read plan: `in` = the plan_decode inputs of the global engine (first n
+ * present of the n+m, index order), `out` = the missing data shards ascending
+ * (write rows only), pass_mask = which inputs are data shards.  Entries of
+ * `bad` naming local parities are ignored.  With no data shard missing the
+ * plan has inputs and no rows. */
+int plan_read(const Code &c, const int32_t *bad, int nbad, Plan *p);
+/* Validate one pattern (GFRS_ERR_INVALID_SHARDS for an index out of range or
+ * repeated, GFRS_ERR_TOO_FEW_SHARDS for more than m global losses) and class
+ * it. */
+int read_pattern_check(const Code &c, const int32_t *bad, int nbad,
+                       ReadPattern *r);
+/* ... and build its plan_read plan (for every class: the slow path wants the
+ * input list too). */
+int read_pattern(const Code &c, const int32_t *bad, int nbad, Plan *p,
+                 ReadPattern *r);
+
+struct ReadBucket {
+  int r = 0;
+  size_t first = 0, count = 0; /* items[first, first+count) */
+  size_t prefix = 0; /* its count+1 frame prefix sums start here
+                        (= first + bucket index) */
+};
+
+struct ReadSchedule {
+  std::vector<gfrs_gitem> items;      /* every bucket's items, back to back;
+                                         inside a bucket ordered by
+                                         descriptor, then by caller index */
+  std::vector<uint64_t> frame_prefix; /* exclusive prefix sums of the frames
+                                         TOUCHED by each item's segment */
+  std::vector<ReadBucket> buckets;    /* ascending r, at most READ_ROWS + 1 */
+  std::vector<int32_t> slow_jobs;     /* caller order */
+};
+
+/* frames [first, last] of a shard that the segment touches */
+inline uint64_t read_first_frame(const gfrs_gjob &j) {
+  return j.seg_off / REPAIR_PAYLOAD;
+}
+inline uint64_t read_last_frame(const gfrs_gjob &j) {
+  return (j.seg_off + j.seg_len - 1) / REPAIR_PAYLOAD;
+}
+
+/* block_len and tactic width: GFRS_ERR_INVALID_BLOCK / _UNSUPPORTED */
+int read_queue_gate(const Code &c, int64_t block_len);
+/* Job validation (gfrs.h, read-queue contract; out_addr = the address of out,
+ * for the alignment rule) and the schedule. */
+int read_schedule(const Code &c, const gfrs_gjob *jobs, int njobs,
+                  const ReadPattern *pats, int npat, uint64_t out_addr,
+                  ReadSchedule *out);
 
 }  // namespace gfrs
 

@@ -384,6 +384,40 @@ class Encoder:
         bits = np.unpackbits(bmn.view(np.uint8), bitorder="little")[:nj]
         return bits.astype(bool).tolist()
 
+    def read_queue(self, out, framed, jobs, patterns, block_len=65536):
+        """Read queue: the degraded GET (datafile.go:410-434 +
+        stream_get.go:382-465) per job in one call - crc32block decode of
+        the surviving shard images and ReconstructData of a segment, in one
+        pass over the images.  framed: flat uint8 device tensor holding the
+        images (what encode_frame_queue wrote); out: flat uint8 device
+        tensor for the rows; jobs: [(img_off, img_stride, shard_len,
+        seg_off, seg_len, out_off, out_stride, pattern)], the image of shard
+        i at byte img_off + i*img_stride of framed, bytes [seg_off,
+        seg_off+seg_len) of data shard i (i < n) at byte
+        out_off + i*out_stride of out; patterns: [[bad shard indices]], an
+        empty list meaning a plain verified read.  Returns the per-job words
+        as a numpy uint32 array: bit i set when input shard i failed a frame
+        CRC (the job's rows are then unspecified)."""
+        assert out.is_cuda and out.is_contiguous()
+        assert framed.is_cuda and framed.is_contiguous()
+        nj = len(jobs)
+        gj = (runtime.GJob * max(1, nj))()
+        for j, job in enumerate(jobs):
+            gj[j] = runtime.GJob(*job, 0)
+        flat = [i for p in patterns for i in p]
+        offs = [0]
+        for p in patterns:
+            offs.append(offs[-1] + len(p))
+        bad = (ctypes.c_int32 * max(1, len(flat)))(*flat)
+        boff = (ctypes.c_int32 * len(offs))(*offs)
+        words = np.zeros(max(1, nj), dtype=np.uint32)
+        check(lib().gfrs_read_queue(
+            self._ctx, out.data_ptr(), framed.data_ptr(), gj, nj, bad, boff,
+            len(patterns), block_len,
+            words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+            "read_queue")
+        return words[:nj]
+
     def synchronize(self):
         check(lib().gfrs_synchronize(self._ctx), "synchronize")
 

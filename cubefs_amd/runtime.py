@@ -161,6 +161,46 @@ class EBucket(ctypes.Structure):
     ]
 
 
+class GJob(ctypes.Structure):
+    """gfrs_gjob: one job of a read queue."""
+    _fields_ = [
+        ("img_off", ctypes.c_uint64),
+        ("img_stride", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("seg_off", ctypes.c_uint64),
+        ("seg_len", ctypes.c_uint64),
+        ("out_off", ctypes.c_uint64),
+        ("out_stride", ctypes.c_uint64),
+        ("pattern", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class GItem(ctypes.Structure):
+    """gfrs_gitem: one work item of a read schedule."""
+    _fields_ = [
+        ("img", ctypes.c_uint64),
+        ("img_stride", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("seg_off", ctypes.c_uint64),
+        ("seg_len", ctypes.c_uint64),
+        ("out", ctypes.c_uint64),
+        ("out_stride", ctypes.c_uint64),
+        ("job", ctypes.c_int32),
+        ("desc", ctypes.c_int32),
+    ]
+
+
+class GBucket(ctypes.Structure):
+    """gfrs_gbucket: one launch of a read schedule."""
+    _fields_ = [
+        ("r", ctypes.c_int32),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -286,6 +326,13 @@ def lib():
             ctypes.POINTER(Tactic), ctypes.POINTER(EJob), ctypes.c_int, i64,
             ctypes.c_int, ctypes.POINTER(EItem), u64p, ip,
             ctypes.POINTER(EBucket), ip, ip]
+        L.gfrs_read_queue.argtypes = [vp, vp, vp, ctypes.POINTER(GJob),
+                                      ctypes.c_int, i32p, i32p, ctypes.c_int,
+                                      i64, u32p]
+        L.gfrs_compute_read_queue_schedule.argtypes = [
+            ctypes.POINTER(Tactic), ctypes.POINTER(GJob), ctypes.c_int, i32p,
+            i32p, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(GItem),
+            u64p, ip, ctypes.POINTER(GBucket), ip, i32p, i32p, i32p, ip]
         _lib = L
     return _lib
 

@@ -495,6 +495,93 @@ int gfrs_encode_frame_queue(gfrs_ctx *ctx, void *framed, void *base,
                             const gfrs_ejob *jobs, int njobs,
                             int64_t block_len);
 
+/* ---- read queue (datafile.go:410-434 + stream_get.go:382-465: the degraded
+ * GET over concurrent blobs - crc32block decode of every shard read, then
+ * ReconstructData on the shards or on a segment of them) ----
+ * Every job names the framed images of its stripe (what
+ * gfrs_encode_frame_queue wrote), an erasure pattern and a segment
+ * [seg_off, seg_off + seg_len) of the raw shards, and gets back that segment
+ * of all n data shards - surviving ones decoded, missing ones rebuilt - and a
+ * word naming the inputs whose frame CRCs did not match.  The images are read
+ * once; no raw shard is materialized.  Patterns are given as for the two
+ * repair queues (bad_idx / bad_off, npat + 1 offsets); jobs, bad_idx, bad_off
+ * and bad_shards are host memory, out and framed device pointers.
+ *
+ * Read-queue contract (pinned by tests/test_gpu_read_queue.py):
+ *  - Per-job result.  Row i (i < n) of job j holds bytes
+ *    [seg_off, seg_off + seg_len) of data shard i: for a missing shard what
+ *    crc32block decode of the surviving images followed by
+ *    ReconstructData(shards, bad) yields, for a surviving shard its own
+ *    decoded bytes.
+ *  - Inputs.  The inputs of a job are the first n present shards among the
+ *    n+m in index order (reedsolomon.go:1453-1466) - the n data shards when
+ *    none of them is bad.  No other image is read; local parities are never
+ *    read, and pattern entries naming them are ignored.
+ *  - Verdict.  Bit i of bad_shards[j] is set exactly when shard i is an input
+ *    of job j and one of its frames touched by the segment - frames
+ *    floor(seg_off / 65532) through floor((seg_off + seg_len - 1) / 65532) -
+ *    stores a CRC that differs from the CRC32-IEEE of its payload.  Only
+ *    those frames are read, and they are read whole.  When a job's word is
+ *    nonzero its declared rows are written with unspecified content; the
+ *    caller adds the named shards to the pattern and resubmits
+ *    (stream_get.go:413-478).  An empty pattern is a plain verified read.
+ *  - Layout.  Image sources need no alignment.  out + out_off and out_stride
+ *    are multiples of 4, and so is seg_off (raw positions and destination
+ *    addresses stay congruent; a caller with an odd offset rounds down and
+ *    skips up to 3 bytes).  framed is never written.  In out only the n
+ *    declared rows of each job are written, seg_len bytes each: nothing
+ *    between rows or between jobs.  Overlapping rows are a caller error (not
+ *    checked).
+ *  - Validation.  Everything is validated before the first launch, and any
+ *    error returns its code and writes nothing:
+ *      GFRS_ERR_INVALID_BLOCK for block_len <= 0 or not a multiple of 4096;
+ *      GFRS_ERR_UNSUPPORTED for any other block_len != 65536, and for a
+ *      tactic of more than 32 global shards (the width of a word);
+ *      every pattern, used by a job or not: GFRS_ERR_INVALID_SHARDS for an
+ *      index out of range or a repeated index, GFRS_ERR_TOO_FEW_SHARDS when
+ *      more than m of the n+m global shards are bad;
+ *      GFRS_ERR_INVALID_SHARDS for njobs <= 0, npat <= 0, a malformed
+ *      bad_off, pattern outside [0, npat), reserved != 0, a misaligned
+ *      seg_off, out + out_off or out_stride, out_stride < seg_len, img_stride
+ *      below the image size, or seg_off + seg_len > shard_len;
+ *      GFRS_ERR_SHARD_NO_DATA for shard_len == 0 or seg_len == 0.
+ *  - Blocking.  The call blocks until the words are ready; it runs on the
+ *    context stream, takes the context mutex once and makes one upload of one
+ *    blob and one sync.
+ *  - Launch bound.  A pattern is classed by R, its number of missing data
+ *    shards.  It is FUSED when R <= 4 and n+m+l <= 16: each of its jobs is
+ *    one work item in the bucket of its R (0..4), so a queue costs at most 5
+ *    kernel launches whatever njobs and npat are.  A copy-only pattern
+ *    (R = 0) of a wider tactic is IDENTITY: one item per data shard in the
+ *    R = 0 bucket.  Every other pattern (R > 4, rebuilds on wider tactics) is
+ *    SLOW: its jobs run one at a time after the launches - the touched
+ *    frames of the inputs are decoded into a context-owned scratch stripe,
+ *    the decode plan runs there and the segment is copied out: same rows and
+ *    words, several launches per job.
+ *  - A job of at most 4096 bytes per shard still occupies one workgroup
+ *    (small jobs are not packed together). */
+typedef struct gfrs_gjob {
+  uint64_t img_off;    /* framed image of shard i at framed + img_off +
+                          i*img_stride, i < n+m+l */
+  uint64_t img_stride; /* any value >= gfrs_crc32b_encode_size(shard_len,
+                          65536); sources need no alignment */
+  uint64_t shard_len;  /* raw shard length, > 0, any value */
+  uint64_t seg_off;    /* first raw byte wanted of every data shard; multiple
+                          of 4 */
+  uint64_t seg_len;    /* > 0, seg_off + seg_len <= shard_len (stream_get.go
+                          shardOffset / shardReadSize) */
+  uint64_t out_off;    /* bytes [seg_off, seg_off+seg_len) of data shard i,
+                          i < n, at out + out_off + i*out_stride */
+  uint64_t out_stride; /* multiple of 4, >= seg_len */
+  int32_t pattern;     /* 0 <= pattern < npat */
+  int32_t reserved;    /* must be 0 */
+} gfrs_gjob;
+
+int gfrs_read_queue(gfrs_ctx *ctx, void *out, const void *framed,
+                    const gfrs_gjob *jobs, int njobs, const int32_t *bad_idx,
+                    const int32_t *bad_off, int npat, int64_t block_len,
+                    uint32_t *bad_shards /* njobs words */);
+
 /* ---- ec.Buffer size math (buf.go:67-133) ---- */
 int gfrs_buffer_sizes(const gfrs_tactic *t, int64_t data_size,
                       int64_t *shard_size, int64_t *ec_data_size,
@@ -519,6 +606,12 @@ enum {
   GFRS_PLAN_RS_RECONSTRUCT_VERIFY = 1,  /* gfrs_reconstruct_verify_batch */
   GFRS_PLAN_LRC_RECONSTRUCT_VERIFY = 2, /* the same, LRC single pass */
   GFRS_PLAN_FUSED_REPAIR = 3,           /* gfrs_repair_batch, fused kernel */
+  GFRS_PLAN_READ = 4,                   /* gfrs_read_queue: `in` = the first n
+                                           present of the n+m shards, `out` =
+                                           the missing data shards ascending
+                                           (all write rows); *colpack returns
+                                           the pass-through set, bit c = in[c]
+                                           is a data shard */
 };
 int gfrs_compute_plan(const gfrs_tactic *t, int kind, const int32_t *bad,
                       int nbad, int cap, int32_t *in, int *nin, int32_t *out,
@@ -632,6 +725,44 @@ int gfrs_compute_encode_queue_schedule(const gfrs_tactic *t,
                                        uint64_t *frame_prefix, int *nitems,
                                        gfrs_ebucket *buckets, int *nbuckets,
                                        int *fused);
+/* GPU-free: what gfrs_read_queue would upload for a queue, with the same
+ * builder, so CPU tests can check it without a device.
+ *   Pattern class: GFRS_GPAT_FUSED patterns (pat_r = R missing data shards,
+ *   0..4) run the fused read kernel over their plan; GFRS_GPAT_IDENTITY ones
+ *   (R = 0 on a tactic wider than 16 shards) run it shard by shard;
+ *   GFRS_GPAT_SLOW ones run one job at a time and are listed in slow_jobs,
+ *   caller order.
+ *   Work items: a fused job is one item of its pattern's descriptor (desc =
+ *   pattern index) in the bucket of its R; an identity job is one item per
+ *   data shard s (desc = npat + s: k = 1, one pass-through input s) in the
+ *   R = 0 bucket.  At most one bucket per R, ascending; bucket b owns
+ *   items[first, first+count), ordered by descriptor, then by caller index,
+ *   and the count+1 exclusive prefix sums of the TOUCHED frames of its items -
+ *   floor((seg_off + seg_len - 1) / 65532) - floor(seg_off / 65532) + 1, not
+ *   ceil(shard_len / 65532) - at frame_prefix[first + b ...].
+ * items holds item_cap entries, frame_prefix item_cap + 5, buckets 5, pat_*
+ * npat, slow_jobs njobs (GFRS_ERR_NOMEM when the schedule is larger).  Returns
+ * the validation codes of gfrs_read_queue, taking out as 4-aligned. */
+enum { GFRS_GPAT_FUSED = 0, GFRS_GPAT_IDENTITY = 1, GFRS_GPAT_SLOW = 2 };
+typedef struct gfrs_gitem {
+  uint64_t img;        /* byte offset in framed of the image of shard 0 */
+  uint64_t img_stride; /* between the job's images */
+  uint64_t shard_len;
+  uint64_t seg_off, seg_len;
+  uint64_t out;        /* byte offset in out of row 0 */
+  uint64_t out_stride; /* between the job's rows */
+  int32_t job;         /* caller's index */
+  int32_t desc;        /* descriptor index */
+} gfrs_gitem;
+typedef struct gfrs_gbucket {
+  int32_t r, first, count, reserved;
+} gfrs_gbucket;
+int gfrs_compute_read_queue_schedule(
+    const gfrs_tactic *t, const gfrs_gjob *jobs, int njobs,
+    const int32_t *bad_idx, const int32_t *bad_off, int npat,
+    int64_t block_len, int item_cap, gfrs_gitem *items,
+    uint64_t *frame_prefix, int *nitems, gfrs_gbucket *buckets, int *nbuckets,
+    int32_t *pat_class, int32_t *pat_r, int32_t *slow_jobs, int *nslow);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);

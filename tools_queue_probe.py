@@ -33,6 +33,19 @@ and gfrs_encode_frame_queue against gfrs_encode_frame_batch, RS(6+3)
  (i) 65536 jobs x 6 KiB: the batch call runs the wave kernel there, the
      queue the frame kernel.
 
+and gfrs_read_queue, RS(12+4) (--only rs):
+
+ (r) uniform  512 jobs x 4 MiB, pattern [1], the whole shard: the queue vs
+     the composition a caller had before it - gfrs_crc32b_decode of the 12
+     inputs of every job, then ONE gfrs_reconstruct_batch(data_only=1) - and
+     vs the yardstick kernel, ONE gfrs_crc32b_decode of a single image of as
+     many frames (the unchanged register-CRC decode kernel: read n framed,
+     write n raw, the memory skeleton of the read kernel); three interleaved
+     medians of queue and yardstick.
+ (s) mixed    the 4096-job size mix of (b), 8 patterns, a quarter of the jobs
+     with segments of 64 KiB or less: the queue vs a per-blob loop of the
+     existing calls (12 decodes, reconstruct, slice copy).
+
 (a) and (d) run on random data with encoded parity; the others on a zeroed buffer
 (a valid stripe: zero parity), since the kernels' work does not depend on
 the data.  One JSON line on stdout; --out also writes it to a file.
@@ -392,6 +405,185 @@ class EncodeProbe:
         return res
 
 
+class ReadProbe:
+    """gfrs_read_queue against the calls a caller had before it, RS(12+4), on
+    zeroed shards (zero parity: a valid stripe; the kernels' work does not
+    depend on the data).  Every image is the crc32block framing of a zero
+    shard, built once per length by gfrs_crc32b_encode and copied."""
+
+    def __init__(self):
+        self.t = codemode.get_tactic("EC12P4")
+        self.enc = ec.Encoder(self.t)
+        self.L = runtime.lib()
+        self.n, self.total = self.t.N, self.t.N + self.t.M
+
+    def image(self, ln):
+        size = self.L.gfrs_crc32b_encode_size(ln, 65536)
+        raw = torch.zeros(ln, dtype=torch.uint8, device="cuda")
+        img = torch.empty(size, dtype=torch.uint8, device="cuda")
+        w = self.L.gfrs_crc32b_encode(self.enc._ctx, img.data_ptr(),
+                                      raw.data_ptr(), ln, 65536)
+        assert w == size, w
+        return img
+
+    def buffers(self, lens, segs, npat, seed=1):
+        """jobs: (img_off, img_stride, ln, seg_off, seg_len, out_off,
+        out_stride, pattern); images at the tight stride, rows at the tight
+        4-aligned stride."""
+        rng = random.Random(seed)
+        jobs, img, out = [], 0, 0
+        for ln, (so, sl) in zip(lens, segs):
+            stride = self.L.gfrs_crc32b_encode_size(ln, 65536)
+            ostride = (sl + 3) // 4 * 4
+            jobs.append((img, stride, ln, so, sl, out, ostride,
+                         rng.randrange(npat)))
+            img += self.total * stride
+            out += self.n * ostride
+        framed = torch.empty(img, dtype=torch.uint8, device="cuda")
+        images = {ln: self.image(ln) for ln in set(lens)}
+        for job in jobs:
+            framed[job[0]:job[0] + self.total * job[1]].view(
+                self.total, job[1]).copy_(images[job[2]])
+        dst = torch.empty(out, dtype=torch.uint8, device="cuda")
+        gj = (runtime.GJob * len(jobs))()
+        for j, job in enumerate(jobs):
+            gj[j] = runtime.GJob(*job, 0)
+        return jobs, framed, dst, gj
+
+    def pattern_args(self, patterns):
+        flat = [i for p in patterns for i in p] or [0]
+        offs = [0]
+        for p in patterns:
+            offs.append(offs[-1] + len(p))
+        self.bads = [((ctypes.c_int32 * max(1, len(p)))(*p), len(p))
+                     for p in patterns]
+        self.inputs = [[i for i in range(self.total) if i not in p][:self.n]
+                       for p in patterns]
+        return ((ctypes.c_int32 * len(flat))(*flat),
+                (ctypes.c_int32 * len(offs))(*offs), len(patterns))
+
+    def queue(self, framed, dst, gj, njobs, pargs):
+        words = (ctypes.c_uint32 * njobs)()
+        rc = self.L.gfrs_read_queue(self.enc._ctx, dst.data_ptr(),
+                                    framed.data_ptr(), gj, njobs, *pargs,
+                                    65536, words)
+        assert rc == 0 and not any(words), rc
+
+    def decode_inputs(self, framed, raw_ptr, job):
+        img_off, stride, ln, _, _, _, _, pat = job
+        size = self.L.gfrs_crc32b_encode_size(ln, 65536)
+        for i in self.inputs[pat]:
+            w = self.L.gfrs_crc32b_decode(
+                self.enc._ctx, raw_ptr + i * ln,
+                framed.data_ptr() + img_off + i * stride, size, 65536)
+            assert w == ln, w
+
+    def uniform(self, njobs, slen, reps, comp_reps):
+        jobs, framed, dst, gj = self.buffers([slen] * njobs,
+                                             [(0, slen)] * njobs, 1)
+        pargs = self.pattern_args(PATTERNS[:1])
+        bad, nbad = self.bads[0]
+        raw = torch.empty(njobs * self.total * slen, dtype=torch.uint8,
+                          device="cuda")
+
+        def composition():
+            for j, job in enumerate(jobs):
+                self.decode_inputs(framed, raw.data_ptr() +
+                                   j * self.total * slen, job)
+            rc = self.L.gfrs_reconstruct_batch(
+                self.enc._ctx, raw.data_ptr(), slen, self.total * slen, njobs,
+                bad, nbad, 1)
+            assert rc == 0, rc
+            self.enc.synchronize()
+
+        # the yardstick: ONE decode of one image of as many full frames as fit
+        # the queue's own destination (the bytes the queue's inputs hold)
+        nframes = njobs * self.n * slen // 65532
+        yard = torch.empty(nframes * 65536, dtype=torch.uint8, device="cuda")
+        yard.view(nframes, 65536).copy_(self.image(65532))
+
+        def yardstick():
+            w = self.L.gfrs_crc32b_decode(self.enc._ctx, dst.data_ptr(),
+                                          yard.data_ptr(), yard.numel(), 65536)
+            assert w == nframes * 65532, w
+
+        res = {"njobs": njobs, "shard_len": slen}
+        for i in (1, 2, 3):
+            res["yardstick_%d" % i] = timed(yardstick, reps)
+            res["queue_%d" % i] = timed(
+                lambda: self.queue(framed, dst, gj, njobs, pargs), reps)
+        res["composition"] = timed(composition, comp_reps)
+        ys = [res["yardstick_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        qs = [res["queue_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        res["yardstick_medians_ms"], res["queue_medians_ms"] = ys, qs
+        res["yardstick_spread"] = round(max(ys) / min(ys) - 1, 4)
+        res["queue_over_yardstick"] = round(statistics.median(qs) /
+                                            statistics.median(ys), 4)
+        res["queue_over_composition"] = round(
+            statistics.median(qs) / res["composition"]["median_ms"], 4)
+        res["moved_GB"] = round(njobs * slen * 2 * self.n / 1e9, 3)
+        for name in ("GFRS_RD_WAVES",):
+            if name in os.environ:
+                res[name] = os.environ[name]
+        return res
+
+    def mixed(self, lens, patterns, reps, loop_reps):
+        rng = random.Random(11)
+        segs = []
+        for ln in lens:
+            if rng.randrange(4) == 0:       # a ranged GET of <= 64 KiB
+                sl = rng.choice([4 * KIB, 16 * KIB, 64 * KIB])
+                segs.append((4 * rng.randrange((ln - sl) // 4 + 1), sl))
+            else:
+                segs.append((0, ln))
+        jobs, framed, dst, gj = self.buffers(lens, segs, len(patterns), seed=1)
+        pargs = self.pattern_args(patterns)
+        raw = torch.empty(self.total * max(lens), dtype=torch.uint8,
+                          device="cuda")
+
+        def loop():
+            for job in jobs:
+                _, _, ln, so, sl, out_off, ostride, pat = job
+                self.decode_inputs(framed, raw.data_ptr(), job)
+                bad, nbad = self.bads[pat]
+                rc = self.L.gfrs_reconstruct_batch(
+                    self.enc._ctx, raw.data_ptr(), ln, self.total * ln, 1,
+                    bad, nbad, 1)
+                assert rc == 0, rc
+                self.enc.synchronize()
+                dst[out_off:out_off + self.n * ostride].view(
+                    self.n, ostride)[:, :sl].copy_(
+                        raw[:self.n * ln].view(self.n, ln)[:, so:so + sl])
+            torch.cuda.synchronize()
+
+        res = {"njobs": len(jobs), "image_bytes": framed.numel(),
+               "out_bytes": dst.numel(), "npat": len(patterns),
+               "ranged_jobs": sum(1 for s, ln in zip(segs, lens)
+                                  if s[1] != ln),
+               "queue": timed(
+                   lambda: self.queue(framed, dst, gj, len(jobs), pargs),
+                   reps),
+               "loop": timed(loop, loop_reps)}
+        res["loop_over_queue"] = round(res["loop"]["median_ms"] /
+                                       res["queue"]["median_ms"], 2)
+        return res
+
+
+def read_main(a, out):
+    p = ReadProbe()
+    out["read_tactic"] = "EC12P4"
+    if "r" in a.only:
+        out["r_read_uniform"] = p.uniform(512 // a.scale, 4 * MIB, reps=7,
+                                          comp_reps=2)
+        torch.cuda.empty_cache()
+    if "s" in a.only:
+        rng = random.Random(7)               # the lengths of (b)
+        lens = [rng.choice([64 * KIB, MIB, 4 * MIB])
+                for _ in range(4096 // a.scale)]
+        out["s_read_mixed"] = p.mixed(lens, PATTERNS, reps=5, loop_reps=1)
+        torch.cuda.empty_cache()
+
+
 def encode_main(a, out):
     p = EncodeProbe()
     out["encode_tactic"] = "EC6P3"
@@ -423,11 +615,14 @@ def main():
                     help="divide every job count by this (dry runs)")
     ap.add_argument("--only", default="abcde",
                     help="which configurations to run, e.g. 'ac'; the "
-                    "encode+frame queue's are 'fpghi' (p = f')")
+                    "encode+frame queue's are 'fpghi' (p = f'), the read "
+                    "queue's 'rs'")
     a = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "scale": a.scale}
     if set(a.only) & set("fpghi"):
         encode_main(a, out)
+    if set(a.only) & set("rs"):
+        read_main(a, out)
     if not set(a.only) & set("abcde"):
         line = json.dumps(out)
         print(line)
