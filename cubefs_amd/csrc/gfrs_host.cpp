@@ -194,11 +194,16 @@ struct Lane {
   }
 };
 
-/* view over either a lane's or the context's stream+scratch */
+struct gfrs_ctx_impl;
+
+/* view over either a lane's or the context's stream+scratch; owner is the
+ * context when the scratch is the context's own (pin_for_write), nullptr
+ * for a lane */
 struct LaneView {
   hipStream_t stream;
   DevBuf *ptr_buf, *fail_buf, *stage_dev;
   PinBuf *stage_pin;
+  gfrs_ctx_impl *owner;
 };
 
 struct gfrs_ctx_impl {
@@ -264,10 +269,13 @@ struct gfrs_ctx_impl {
     return GFRS_OK;
   }
 
-  /* gfrs_shard_write_batch returns with its id upload still queued; the
-   * next call must not refill the pinned staging before that copy ran */
-  hipEvent_t ids_ev = nullptr;
-  bool ids_pending = false;
+  /* gfrs_shard_write_batch returns with its id upload out of stage_pin
+   * still queued; no later call may write stage_pin (or free it to grow
+   * it) before that copy ran.  pin_ev is recorded behind the copy and
+   * pin_for_write waits it out.  Every other call that uploads from
+   * stage_pin synchronizes its stream before it returns. */
+  hipEvent_t pin_ev = nullptr;
+  bool pin_pending = false;
 
   /* stream-lane pool for concurrent foreground (single-stripe) calls;
    * empty when GFRS_LANES=0 or after gfrs_set_stream pins a caller
@@ -291,7 +299,7 @@ struct gfrs_ctx_impl {
     for (int i = 0; i < 2; i++)
       if (aux_ev[i]) hipEventDestroy(aux_ev[i]);
     if (aux_done) hipEventDestroy(aux_done);
-    if (ids_ev) hipEventDestroy(ids_ev);
+    if (pin_ev) hipEventDestroy(pin_ev);
   }
 };
 
@@ -308,11 +316,11 @@ struct StreamGuard {
 
 static inline LaneView view_of(gfrs_ctx_impl *c) {
   return LaneView{c->stream, &c->ptr_buf, &c->fail_buf, &c->stage_dev,
-                  &c->stage_pin};
+                  &c->stage_pin, c};
 }
 static inline LaneView view_of(Lane *L) {
   return LaneView{L->stream, &L->ptr_buf, &L->fail_buf, &L->stage_dev,
-                  &L->stage_pin};
+                  &L->stage_pin, nullptr};
 }
 
 /* The plans a context keeps for its lifetime: global encode, per-AZ local
@@ -449,8 +457,19 @@ void gfrs_destroy(gfrs_ctx *ctx) { delete reinterpret_cast<gfrs_ctx_impl *>(ctx)
 int gfrs_set_stream(gfrs_ctx *ctx, void *hip_stream) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
   std::lock_guard<std::mutex> lk(c->mu);
-  c->stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream)
-                         : c->own_stream;
+  hipStream_t next = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream)
+                                : c->own_stream;
+  if (next != c->stream) {
+    /* the async batch calls leave work queued that reads the context's
+     * scratch (ptr_buf, the plans); the next stream is not ordered against
+     * it, so drain it here - this is not a hot call.  A caller stream that
+     * has been destroyed meanwhile has nothing queued: its error is
+     * dropped. */
+    StreamGuard g(c);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) (void)hipGetLastError();
+    c->pin_pending = false;
+  }
+  c->stream = next;
   /* a caller-pinned stream implies caller-managed ordering: foreground
    * calls then issue on that one stream instead of fanning out */
   c->user_stream = hip_stream != nullptr;
@@ -490,14 +509,34 @@ int gfrs_probe_perm(void) {
 
 namespace gfrs {
 
+/* The one way the host gets to write a view's pinned staging: n bytes of
+ * it, after any upload out of it that an earlier call left queued has run.
+ * Device-side scratch reuse is ordered by the stream; the host's writes to
+ * the staging are ordered by nothing but this wait (it also precedes the
+ * free that grows the buffer).  Nothing pending - the usual case - costs
+ * one flag test; a lane's staging is never left pending (owner == nullptr),
+ * every lane call syncs its stream under the lane mutex. */
+static int pin_for_write(const LaneView &lv, size_t n, uint8_t **pin) {
+  gfrs_ctx_impl *c = lv.owner;
+  if (c && c->pin_pending) {
+    HIP_TRY(hipEventSynchronize(c->pin_ev));
+    c->pin_pending = false;
+  }
+  int rc = lv.stage_pin->ensure(n);
+  if (rc != GFRS_OK) return rc;
+  *pin = (uint8_t *)lv.stage_pin->p;
+  return GFRS_OK;
+}
+
 /* Upload a pointer table for pointer-mode launches (stream-ordered, so
  * reuse of the scratch buffer is safe across calls on one stream). */
 static int upload_ptrs(const LaneView &lv, void *const *shards, int nshards) {
   int rc = lv.ptr_buf->ensure(size_t(nshards) * 8);
   if (rc != GFRS_OK) return rc;
   /* small, use pinned staging for async copy */
-  if ((rc = lv.stage_pin->ensure(size_t(nshards) * 8)) != GFRS_OK) return rc;
-  memcpy(lv.stage_pin->p, shards, size_t(nshards) * 8);
+  uint8_t *pin;
+  if ((rc = pin_for_write(lv, size_t(nshards) * 8, &pin)) != GFRS_OK) return rc;
+  memcpy(pin, shards, size_t(nshards) * 8);
   HIP_TRY(hipMemcpyAsync(lv.ptr_buf->p, lv.stage_pin->p, size_t(nshards) * 8,
                          hipMemcpyHostToDevice, lv.stream));
   return GFRS_OK;
@@ -513,8 +552,8 @@ static int stage_host_stripe(const LaneView &lv, void *const *shards,
   const size_t tot = size_t(nshards) * shard_len;
   int rc;
   if ((rc = lv.stage_dev->ensure(tot + dev_slack)) != GFRS_OK) return rc;
-  if ((rc = lv.stage_pin->ensure(tot)) != GFRS_OK) return rc;
-  uint8_t *pin = (uint8_t *)lv.stage_pin->p;
+  uint8_t *pin;
+  if ((rc = pin_for_write(lv, tot, &pin)) != GFRS_OK) return rc;
   for (int i = 0; i < ncopy; i++)
     if (!present || present[i])
       memcpy(pin + size_t(i) * shard_len, shards[i], shard_len);
@@ -525,19 +564,15 @@ static int stage_host_stripe(const LaneView &lv, void *const *shards,
 
 /* Stage n bids then n vuids into c->ptr_buf (stream-ordered scratch reuse)
  * through the pinned staging.  gfrs_shard_write_batch returns with this
- * upload still queued, so a queued earlier one is waited out before the
- * staging is refilled. */
+ * upload still queued (pin_pending). */
 static int stage_ids(gfrs_ctx_impl *c, const uint64_t *bids,
                      const uint64_t *vuids, size_t n) {
   const size_t idbytes = n * 8;
   int rc;
-  if (c->ids_pending) {
-    HIP_TRY(hipEventSynchronize(c->ids_ev));
-    c->ids_pending = false;
-  }
-  if ((rc = c->stage_pin.ensure(idbytes * 2)) != GFRS_OK) return rc;
-  memcpy(c->stage_pin.p, bids, idbytes);
-  memcpy((uint8_t *)c->stage_pin.p + idbytes, vuids, idbytes);
+  uint8_t *pin;
+  if ((rc = pin_for_write(view_of(c), idbytes * 2, &pin)) != GFRS_OK) return rc;
+  memcpy(pin, bids, idbytes);
+  memcpy(pin + idbytes, vuids, idbytes);
   if ((rc = c->ptr_buf.ensure(idbytes * 2)) != GFRS_OK) return rc;
   HIP_TRY(hipMemcpyAsync(c->ptr_buf.p, c->stage_pin.p, idbytes * 2,
                          hipMemcpyHostToDevice, c->stream));
@@ -1162,15 +1197,16 @@ int gfrs_shard_write_batch(gfrs_ctx *ctx, void *dst, size_t dst_stride,
   /* ship the raw id arrays; the finalize kernel builds the 32 B headers
    * (shard.go:241-261) on device - host-side construction was the
    * bottleneck at millions of shards per call */
-  /* this call is async, so the next call must not refill the staging
-   * before this upload ran (the legacy repair path issues one call per
-   * lost column back to back: column b then got column b+1's ids):
-   * stage_ids waits for the event recorded here */
-  if (!c->ids_ev)
-    HIP_TRY(hipEventCreateWithFlags(&c->ids_ev, hipEventDisableTiming));
+  /* this call is async, so no later call may refill the staging before
+   * this upload ran (the legacy repair path issues one call per lost
+   * column back to back: column b then got column b+1's ids; a pointer
+   * table or a host stripe of the next call would do the same):
+   * pin_for_write waits for the event recorded here */
+  if (!c->pin_ev)
+    HIP_TRY(hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming));
   if ((rc = stage_ids(c, bids, vuids, size_t(nshards))) != GFRS_OK) return rc;
-  HIP_TRY(hipEventRecord(c->ids_ev, c->stream));
-  c->ids_pending = true;
+  HIP_TRY(hipEventRecord(c->pin_ev, c->stream));
+  c->pin_pending = true;
   const uint64_t *ids = (const uint64_t *)c->ptr_buf.p;
   /* framed body at +32 */
   launch_crc_encode((uint8_t *)dst + 32, dst_stride, (const uint8_t *)src,

@@ -43,6 +43,21 @@
  * included, for every erasure pattern and whichever surviving column is
  * corrupted; bad_block / err of the crc32block, sized-coder and shard-image
  * entry points equal the reference's answer for the same image.
+ *
+ * Ordering contract (pinned by tests/test_gpu_sequences.py): the declared
+ * outputs of a call are what that call alone would produce, whatever calls
+ * follow it on the same context, from any thread, with or without an
+ * intervening gfrs_synchronize.  The async batch calls return with their
+ * work - and the uploads of their ids that feed it - queued on the context's
+ * stream; a later call that needs the scratch they still read waits for
+ * that upload on the host (only then; an idle context pays one flag test),
+ * everything else is ordered by the stream.  The caller's side of it: the
+ * buffers handed to an async call stay untouched until gfrs_synchronize, and
+ * two calls whose declared outputs overlap are the caller's to order.
+ * gfrs_set_stream drains the stream the context leaves before it switches,
+ * so nothing queued on the previous stream is still reading the context's
+ * scratch when the first call on the new stream reuses it, and every output
+ * of the calls issued before the switch is complete when it returns.
  */
 #ifndef GFRS_H
 #define GFRS_H
@@ -105,7 +120,10 @@ const char *gfrs_version(void);
 int gfrs_device_count(void);
 
 /* Optional: run on an existing HIP stream (e.g. torch's). stream==NULL
- * reverts to the context's own stream. */
+ * reverts to the context's own stream.  Blocks until the work this context
+ * queued on the stream it leaves is done (ordering contract above); not a
+ * call for a hot path.  The stream that is left may have been destroyed by
+ * its owner already. */
 int gfrs_set_stream(gfrs_ctx *ctx, void *hip_stream);
 int gfrs_synchronize(gfrs_ctx *ctx);
 

@@ -9,6 +9,10 @@ output.  check() compares the whole arena, so every byte that is not a
 declared output (guards, inter-stripe / inter-image padding, all inputs)
 must come back bit-identical.  Regions the ABI leaves unspecified are
 masked explicitly.
+
+Every call is a Step with three phases - prepare, issue, check - so that
+tests/_sequence.py can issue several calls back to back before it checks
+any of them; the run_* helpers are compositions of steps run one at a time.
 """
 import ctypes
 import functools
@@ -48,6 +52,9 @@ class Arena:
         self.dev.copy_(torch.from_numpy(self.host))
         torch.cuda.synchronize()
 
+    def read(self):
+        return self.dev.cpu().numpy()
+
     def expect(self):
         """Copy of the pre-call arena; overwrite declared outputs in it."""
         return self.host.copy()
@@ -55,7 +62,7 @@ class Arena:
     def check(self, want, unspecified=(), what=""):
         """Whole-arena bit comparison; `unspecified` = [(payload_off, n)]."""
         torch.cuda.synchronize()
-        got = self.dev.cpu().numpy()
+        got = self.read()
         if unspecified:
             got = got.copy()
             want = want.copy()
@@ -70,6 +77,27 @@ class Arena:
             "%s: %d bytes differ, first at payload offset %d (payload %d "
             "bytes; negative / beyond = guard), got %d want %d" %
             (what, bad.size, first, self.nbytes, got[bad[0]], want[bad[0]]))
+
+
+class HostArena(Arena):
+    """The same guarded image in host memory, for GFRS_MEM_HOST calls:
+    upload() takes the live copy the call works on, ptr points into it and
+    check() compares it."""
+
+    def __init__(self, dev, nbytes, delta=0, seed=0, guard=GUARD):
+        self.off = guard + delta
+        self.nbytes = nbytes
+        rng = np.random.default_rng(0xA7E4A ^ (seed * 7919 + nbytes))
+        self.host = rng.integers(0, 256, guard + delta + nbytes + guard,
+                                 dtype=np.uint8)
+        self.live = self.ptr = None
+
+    def upload(self):
+        self.live = self.host.copy()
+        self.ptr = self.live.ctypes.data + self.off
+
+    def read(self):
+        return self.live
 
 
 class Stripes:
@@ -202,63 +230,6 @@ def load_stripes(a, lay, ref, skip=()):
                 a.put(lay.off(s, i), ref[s, i])
 
 
-# ---- one-call runners: each does call + whole-arena check ------------------
-
-def run_rs_apply(dev, t, ref, pad=0, delta=0, bad=(1, 7), what=""):
-    """encode_batch, verify_batch (one corrupt stripe) and
-    reconstruct_verify_batch on one layout, arena-checked."""
-    enc = encoder(t)
-    ns, total, slen = ref.shape
-    lay = Stripes(ns, total, slen, pad)
-    a = Arena(dev, lay.nbytes, delta, seed=5)
-    load_stripes(a, lay, ref, skip=range(t.N, total))
-    a.upload()
-    ok(L().gfrs_encode_batch(enc._ctx, vp(a.ptr), slen, lay.stride, ns),
-       what + " encode_batch")
-    sync(enc)
-    want = a.expect()
-    for s in range(ns):
-        for i in range(t.N, total):
-            a.put(lay.off(s, i), ref[s, i], want)
-    a.check(want, what=what + " encode_batch")
-
-    hit = ns - 2
-    a = Arena(dev, lay.nbytes, delta, seed=6)
-    load_stripes(a, lay, ref)
-    a.host[a.off + lay.off(hit, t.N) + slen - 1] ^= 0x40
-    a.upload()
-    bm = bitmap(ns)
-    ok(L().gfrs_verify_batch(enc._ctx, vp(a.ptr), slen, lay.stride, ns, bm),
-       what + " verify_batch")
-    assert bits(bm, ns) == [hit], (what, bits(bm, ns))
-    a.check(a.expect(), what=what + " verify_batch")
-
-    bad = list(bad)
-    a = Arena(dev, lay.nbytes, delta, seed=7)
-    load_stripes(a, lay, ref, skip=bad)
-    a.upload()
-    bm = bitmap(ns)
-    ok(L().gfrs_reconstruct_verify_batch(enc._ctx, vp(a.ptr), slen,
-                                         lay.stride, ns, i32s(bad), len(bad),
-                                         bm), what + " reconstruct_verify")
-    sync(enc)
-    assert bits(bm, ns) == [], (what, bits(bm, ns))
-    want = a.expect()
-    for s in range(ns):
-        for i in bad:
-            a.put(lay.off(s, i), ref[s, i], want)
-    a.check(want, what=what + " reconstruct_verify")
-
-    a = Arena(dev, lay.nbytes, delta, seed=8)
-    load_stripes(a, lay, ref, skip=bad)
-    a.upload()
-    ok(L().gfrs_reconstruct_batch(enc._ctx, vp(a.ptr), slen, lay.stride, ns,
-                                  i32s(bad), len(bad), 0),
-       what + " reconstruct_batch")
-    sync(enc)
-    a.check(want_like(a, lay, ref, bad), what=what + " reconstruct_batch")
-
-
 def want_like(a, lay, ref, filled):
     want = a.expect()
     for s in range(lay.ns):
@@ -275,220 +246,821 @@ def _raw(nsh, slen, seed):
     return arr
 
 
+# ---- three-phase steps -------------------------------------------------------
+
+class Step:
+    """One ABI call in three phases, so that a test can put other calls
+    between the issue of a call and its check (tests/_sequence.py):
+
+      prepare(dev)  host image, oracle expectation, upload, every ctypes
+                    argument; builds fresh arenas each time it is called
+      issue(enc)    the ABI call only: no gfrs_synchronize, no torch sync;
+                    return code and host outputs are kept, not looked at
+      check(enc)    gfrs_synchronize, then every assertion: return code,
+                    host outputs, whole-arena comparison
+
+    blocking: the call synchronizes the context's stream before it returns
+    (False: it returns with its work queued)."""
+    blocking = True
+    what = ""
+
+    def run(self, dev, enc):
+        self.prepare(dev)
+        self.issue(enc)
+        self.check(enc)
+        return self
+
+
+class _StripeStep(Step):
+    """A strided batch of oracle stripes in one arena."""
+
+    def __init__(self, t, ref, pad=0, delta=0, seed=0, what=""):
+        self.t, self.ref, self.what = t, ref, what
+        self.ns, self.total, self.slen = ref.shape
+        self.lay = Stripes(self.ns, self.total, self.slen, pad)
+        self.delta, self.seed = delta, seed
+
+    def arena(self, dev, skip=()):
+        a = Arena(dev, self.lay.nbytes, self.delta, seed=self.seed)
+        load_stripes(a, self.lay, self.ref, skip=skip)
+        return a
+
+
+class EncodeBatch(_StripeStep):
+    blocking = False
+
+    def __init__(self, t, ref, pad=0, delta=0, seed=5, what=""):
+        super().__init__(t, ref, pad, delta, seed, what + " encode_batch")
+
+    def prepare(self, dev):
+        par = range(self.t.N, self.total)
+        self.a = self.arena(dev, skip=par)
+        self.a.upload()
+        self.want = want_like(self.a, self.lay, self.ref, par)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_encode_batch(enc._ctx, vp(self.a.ptr), self.slen,
+                                        self.lay.stride, self.ns)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        self.a.check(self.want, what=self.what)
+
+
+class VerifyBatch(_StripeStep):
+    """One bit flipped in the last byte of the first parity of stripe
+    `hit`; that stripe and no other is reported."""
+
+    def __init__(self, t, ref, pad=0, delta=0, hit=None, seed=6, what=""):
+        super().__init__(t, ref, pad, delta, seed, what + " verify_batch")
+        self.hit = self.ns - 2 if hit is None else hit
+
+    def prepare(self, dev):
+        a = self.a = self.arena(dev)
+        a.host[a.off + self.lay.off(self.hit, self.t.N) + self.slen - 1] \
+            ^= 0x40
+        a.upload()
+        self.bm = bitmap(self.ns)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_verify_batch(enc._ctx, vp(self.a.ptr), self.slen,
+                                        self.lay.stride, self.ns, self.bm)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        assert bits(self.bm, self.ns) == [self.hit], \
+            (self.what, bits(self.bm, self.ns))
+        self.a.check(self.a.expect(), what=self.what)
+
+
+class ReconstructVerifyBatch(_StripeStep):
+    def __init__(self, t, ref, bad=(1, 7), pad=0, delta=0, seed=7, what=""):
+        super().__init__(t, ref, pad, delta, seed,
+                         what + " reconstruct_verify")
+        self.bad = list(bad)
+
+    def prepare(self, dev):
+        self.a = self.arena(dev, skip=self.bad)
+        self.a.upload()
+        self.bm = bitmap(self.ns)
+        self.badv = i32s(self.bad)
+        self.want = want_like(self.a, self.lay, self.ref, self.bad)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_reconstruct_verify_batch(
+            enc._ctx, vp(self.a.ptr), self.slen, self.lay.stride, self.ns,
+            self.badv, len(self.bad), self.bm)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        assert bits(self.bm, self.ns) == [], \
+            (self.what, bits(self.bm, self.ns))
+        self.a.check(self.want, what=self.what)
+
+
+class ReconstructBatch(_StripeStep):
+    blocking = False
+
+    def __init__(self, t, ref, bad=(1, 7), pad=0, delta=0, seed=8, what=""):
+        super().__init__(t, ref, pad, delta, seed,
+                         what + " reconstruct_batch")
+        self.bad = list(bad)
+
+    def prepare(self, dev):
+        self.a = self.arena(dev, skip=self.bad)
+        self.a.upload()
+        self.badv = i32s(self.bad)
+        self.want = want_like(self.a, self.lay, self.ref, self.bad)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_reconstruct_batch(
+            enc._ctx, vp(self.a.ptr), self.slen, self.lay.stride, self.ns,
+            self.badv, len(self.bad), 0)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        self.a.check(self.want, what=self.what)
+
+
+def run_rs_apply(dev, t, ref, pad=0, delta=0, bad=(1, 7), what=""):
+    """encode_batch, verify_batch (one corrupt stripe),
+    reconstruct_verify_batch and reconstruct_batch on one layout,
+    arena-checked."""
+    enc = encoder(t)
+    for step in (EncodeBatch(t, ref, pad, delta, what=what),
+                 VerifyBatch(t, ref, pad, delta, what=what),
+                 ReconstructVerifyBatch(t, ref, bad, pad, delta, what=what),
+                 ReconstructBatch(t, ref, bad, pad, delta, what=what)):
+        step.run(dev, enc)
+
+
+# ---- crc32block, shard images, sized coder -----------------------------------
+
+class _RowStep(Step):
+    """nsh raw shards (source stride padded by `pad`, base at `delta`) and
+    their images as rows (stride padded by `extra`)."""
+
+    def __init__(self, slen, nsh, pad=0, delta=0, extra=0, seed=0, raw_seed=1,
+                 what=""):
+        self.slen, self.nsh, self.what = slen, nsh, what
+        self.pad, self.delta, self.extra, self.seed = pad, delta, extra, seed
+        self.raw = _raw(nsh, slen, raw_seed)
+
+    def source(self, dev, rows, seed):
+        """The arena holding `rows` (a list of equal-length images) as a
+        padded one-shard-per-stripe batch."""
+        lay = Stripes(len(rows), 1, rows[0].size, self.pad)
+        a = Arena(dev, lay.nbytes, self.delta, seed=seed)
+        for j, r in enumerate(rows):
+            a.put(lay.off(j, 0), r)
+        return a, lay
+
+    def dest(self, dev, row_len, seed):
+        rows = Rows(self.nsh, row_len, self.extra)
+        dst = Arena(dev, rows.nbytes, 4 if self.extra else 0, seed=seed)
+        dst.upload()
+        return dst, rows
+
+
+class CrcEncodeBatch(_RowStep):
+    blocking = False
+
+    def __init__(self, slen, nsh, pad=0, delta=0, extra=0, seed=20, what=""):
+        super().__init__(slen, nsh, pad, delta, extra, seed, 1,
+                         what + " crc encode")
+
+    def prepare(self, dev):
+        self.src, self.srows = self.source(dev, list(self.raw), self.seed)
+        self.src.upload()
+        self.dst, self.rows = self.dest(dev, enc_size(self.slen),
+                                        self.seed + 1)
+        self.want = self.dst.expect()
+        for j in range(self.nsh):
+            self.dst.put(self.rows.off(j),
+                         oracle.crc32b_encode(self.raw[j].copy()), self.want)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_crc32b_encode_batch(
+            enc._ctx, vp(self.dst.ptr), self.rows.stride, vp(self.src.ptr),
+            self.srows.stride, self.slen, BLOCK, self.nsh)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        self.dst.check(self.want, what=self.what)
+        self.src.check(self.src.expect(), what=self.what + " source")
+
+
+class CrcVerifyBatch(_RowStep):
+    """The framed images as the (possibly misaligned) source; the last
+    payload byte of image `hit` is flipped."""
+
+    def __init__(self, slen, nsh, pad=0, delta=0, hit=None, seed=22, what=""):
+        super().__init__(slen, nsh, pad, delta, 0, seed, 1,
+                         what + " crc verify")
+        self.hit = nsh - 2 if hit is None else hit
+        self.fl = enc_size(slen)
+
+    def prepare(self, dev):
+        frames = [oracle.crc32b_encode(self.raw[j].copy())
+                  for j in range(self.nsh)]
+        a, self.frows = self.source(dev, frames, self.seed)
+        a.host[a.off + self.frows.off(self.hit, 0) + self.fl - 1] ^= 1
+        a.upload()
+        self.a = a
+        self.badb = (ctypes.c_int64 * self.nsh)()
+
+    def issue(self, enc):
+        self.rc = L().gfrs_crc32b_verify_batch(
+            enc._ctx, vp(self.a.ptr), self.frows.stride, self.fl, BLOCK,
+            self.nsh, self.badb)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        assert list(self.badb) == [(self.fl - 1) // BLOCK if j == self.hit
+                                   else -1 for j in range(self.nsh)], \
+            (self.what, list(self.badb))
+        self.a.check(self.a.expect(), what=self.what)
+
+
+class CrcDecode(Step):
+    """Decode image j out of a prepared CrcVerifyBatch's arena: the raw
+    shard for a clean image, GFRS_ERR_MISMATCHED_CRC (and an unspecified
+    destination) for the flipped one; the source stays untouched."""
+
+    def __init__(self, images, j, seed=23, what=""):
+        self.images, self.j, self.seed = images, j, seed
+        self.what = what + " crc decode"
+
+    def prepare(self, dev):
+        v = self.images
+        self.out = Arena(dev, v.slen, 0, seed=self.seed)
+        self.out.upload()
+        self.src = v.a.ptr + v.frows.off(self.j, 0)
+
+    def issue(self, enc):
+        v = self.images
+        self.n = L().gfrs_crc32b_decode(enc._ctx, vp(self.out.ptr),
+                                        vp(self.src), v.fl, BLOCK)
+
+    def check(self, enc):
+        v = self.images
+        sync(enc)
+        if self.j == v.hit:
+            assert self.n == -9, (self.what, self.n)
+        else:
+            assert self.n == v.slen, (self.what, self.n)
+            want = self.out.expect()
+            self.out.put(0, v.raw[self.j], want)
+            self.out.check(want, what=self.what)
+        v.a.check(v.a.expect(), what=self.what + " source")
+
+
 def run_crc(dev, enc, slen, nsh, pad=0, delta=0, extra=0, what=""):
-    """crc32b encode_batch, verify_batch (one bad shard) and a
-    single-shard decode, arena-checked against the oracle framing."""
-    raw = _raw(nsh, slen, 1)
-    frames = [oracle.crc32b_encode(raw[j].copy()) for j in range(nsh)]
-    fl = enc_size(slen)
-    srows = Stripes(nsh, 1, slen, pad)
-    src = Arena(dev, srows.nbytes, delta, seed=20)
-    for j in range(nsh):
-        src.put(srows.off(j, 0), raw[j])
-    src.upload()
-    rows = Rows(nsh, fl, extra)
-    dst = Arena(dev, rows.nbytes, 4 if extra else 0, seed=21)
-    dst.upload()
-    ok(L().gfrs_crc32b_encode_batch(enc._ctx, vp(dst.ptr), rows.stride,
-                                    vp(src.ptr), srows.stride, slen, BLOCK,
-                                    nsh), what + " crc encode")
-    sync(enc)
-    want = dst.expect()
-    for j in range(nsh):
-        dst.put(rows.off(j), frames[j], want)
-    dst.check(want, what=what + " crc encode")
-    src.check(src.expect(), what=what + " crc encode source")
+    """crc32b encode_batch, verify_batch (one bad shard) and two
+    single-shard decodes (clean, bad), arena-checked against the oracle
+    framing."""
+    CrcEncodeBatch(slen, nsh, pad, delta, extra, what=what).run(dev, enc)
+    v = CrcVerifyBatch(slen, nsh, pad, delta, what=what).run(dev, enc)
+    CrcDecode(v, 0, what=what).run(dev, enc)
+    CrcDecode(v, v.hit, what=what).run(dev, enc)
 
-    # verify: the framed images are now the (possibly misaligned) source
-    frows = Stripes(nsh, 1, fl, pad)
-    a = Arena(dev, frows.nbytes, delta, seed=22)
-    for j in range(nsh):
-        a.put(frows.off(j, 0), frames[j])
-    hit = nsh - 2
-    a.host[a.off + frows.off(hit, 0) + fl - 1] ^= 1  # last payload byte
-    a.upload()
-    badb = (ctypes.c_int64 * nsh)()
-    ok(L().gfrs_crc32b_verify_batch(enc._ctx, vp(a.ptr), frows.stride, fl,
-                                    BLOCK, nsh, badb), what + " crc verify")
-    assert list(badb) == [(fl - 1) // BLOCK if j == hit else -1
-                          for j in range(nsh)], (what, list(badb))
-    a.check(a.expect(), what=what + " crc verify")
 
-    # decode shard 0 (clean) out of the same arena, then the bad shard
-    out = Arena(dev, slen, 0, seed=23)
-    out.upload()
-    n = L().gfrs_crc32b_decode(enc._ctx, vp(out.ptr), vp(a.ptr), fl, BLOCK)
-    assert n == slen, (what, n)
-    want = out.expect()
-    out.put(0, raw[0], want)
-    out.check(want, what=what + " crc decode")
-    n = L().gfrs_crc32b_decode(enc._ctx, vp(out.ptr),
-                               vp(a.ptr + frows.off(hit, 0)), fl, BLOCK)
-    assert n == -9, (what, n)
-    a.check(a.expect(), what=what + " crc decode source")
+def shard_ids(nsh, k=0):
+    """Distinct bids and vuids; k selects another set."""
+    return ([(1 << 40) | (j + 1000 * k) for j in range(nsh)],
+            [0xABCDEF00 + j + 4096 * k for j in range(nsh)])
+
+
+class ShardWriteBatch(_RowStep):
+    blocking = False
+
+    def __init__(self, slen, nsh, pad=0, delta=0, extra=0, ids=0, seed=24,
+                 what=""):
+        super().__init__(slen, nsh, pad, delta, extra, seed, 3,
+                         what + " shard write")
+        self.bids, self.vuids = shard_ids(nsh, ids)
+
+    def prepare(self, dev):
+        self.src, self.srows = self.source(dev, list(self.raw), self.seed)
+        self.src.upload()
+        self.dst, self.rows = self.dest(dev, disk_size(self.slen),
+                                        self.seed + 1)
+        self.want = self.dst.expect()
+        for j in range(self.nsh):
+            self.dst.put(self.rows.off(j),
+                         oracle.shard_write(self.raw[j].copy(),
+                                            bid=self.bids[j],
+                                            vuid=self.vuids[j]), self.want)
+        self.args = (u64s(self.bids), u64s(self.vuids))
+
+    def issue(self, enc):
+        self.rc = L().gfrs_shard_write_batch(
+            enc._ctx, vp(self.dst.ptr), self.rows.stride, vp(self.src.ptr),
+            self.srows.stride, self.slen, BLOCK, self.args[0], self.args[1],
+            self.nsh)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        self.dst.check(self.want, what=self.what)
+        self.src.check(self.src.expect(), what=self.what + " source")
+
+
+class ShardParseBatch(_RowStep):
+    """The oracle's images as the source; the last body byte of image
+    `hit` is flipped."""
+
+    def __init__(self, slen, nsh, pad=0, delta=0, hit=None, seed=26, what=""):
+        super().__init__(slen, nsh, pad, delta, 0, seed, 3,
+                         what + " shard parse")
+        self.bids, self.vuids = shard_ids(nsh)
+        self.hit = nsh - 3 if hit is None else hit
+        self.fl = enc_size(slen)
+
+    def prepare(self, dev):
+        imgs = [oracle.shard_write(self.raw[j].copy(), bid=self.bids[j],
+                                   vuid=self.vuids[j])
+                for j in range(self.nsh)]
+        a, self.irows = self.source(dev, imgs, self.seed)
+        a.host[a.off + self.irows.off(self.hit, 0) + 32 + self.fl - 1] ^= 0x80
+        a.upload()
+        self.a = a
+        self.meta = (ctypes.c_uint64 * (4 * self.nsh))()
+        self.badb = (ctypes.c_int64 * self.nsh)()
+
+    def issue(self, enc):
+        self.rc = L().gfrs_shard_parse_batch(
+            enc._ctx, vp(self.a.ptr), self.irows.stride, self.slen, BLOCK,
+            self.meta, self.badb, self.nsh)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        meta, what = self.meta, self.what
+        for j in range(self.nsh):
+            assert (meta[4 * j], meta[4 * j + 1], meta[4 * j + 2]) == \
+                (self.bids[j], self.vuids[j], self.slen), (what, j)
+            err = ctypes.c_int64(meta[4 * j + 3]).value
+            assert err == (-9 if j == self.hit else 0), (what, j, err)
+            assert self.badb[j] == ((self.fl - 1) // BLOCK if j == self.hit
+                                    else -1), (what, j)
+        self.a.check(self.a.expect(), what=what)
 
 
 def run_shard_images(dev, enc, slen, nsh, pad=0, delta=0, extra=0, what=""):
     """shard_write_batch then shard_parse_batch (one corrupt image)."""
-    raw = _raw(nsh, slen, 3)
-    bids = [(1 << 40) | j for j in range(nsh)]
-    vuids = [0xABCDEF00 + j for j in range(nsh)]
-    imgs = [oracle.shard_write(raw[j].copy(), bid=bids[j], vuid=vuids[j])
-            for j in range(nsh)]
-    dl = disk_size(slen)
-    srows = Stripes(nsh, 1, slen, pad)
-    src = Arena(dev, srows.nbytes, delta, seed=24)
-    for j in range(nsh):
-        src.put(srows.off(j, 0), raw[j])
-    src.upload()
-    rows = Rows(nsh, dl, extra)
-    dst = Arena(dev, rows.nbytes, 4 if extra else 0, seed=25)
-    dst.upload()
-    ok(L().gfrs_shard_write_batch(enc._ctx, vp(dst.ptr), rows.stride,
-                                  vp(src.ptr), srows.stride, slen, BLOCK,
-                                  u64s(bids), u64s(vuids), nsh),
-       what + " shard write")
-    sync(enc)
-    want = dst.expect()
-    for j in range(nsh):
-        dst.put(rows.off(j), imgs[j], want)
-    dst.check(want, what=what + " shard write")
-    src.check(src.expect(), what=what + " shard write source")
+    ShardWriteBatch(slen, nsh, pad, delta, extra, what=what).run(dev, enc)
+    ShardParseBatch(slen, nsh, pad, delta, what=what).run(dev, enc)
 
-    irows = Stripes(nsh, 1, dl, pad)
-    a = Arena(dev, irows.nbytes, delta, seed=26)
-    for j in range(nsh):
-        a.put(irows.off(j, 0), imgs[j])
-    hit = nsh - 3
-    fl = enc_size(slen)
-    a.host[a.off + irows.off(hit, 0) + 32 + fl - 1] ^= 0x80  # last body byte
-    a.upload()
-    meta = (ctypes.c_uint64 * (4 * nsh))()
-    badb = (ctypes.c_int64 * nsh)()
-    ok(L().gfrs_shard_parse_batch(enc._ctx, vp(a.ptr), irows.stride, slen,
-                                  BLOCK, meta, badb, nsh),
-       what + " shard parse")
-    for j in range(nsh):
-        assert (meta[4 * j], meta[4 * j + 1], meta[4 * j + 2]) == \
-            (bids[j], vuids[j], slen), (what, j)
-        err = ctypes.c_int64(meta[4 * j + 3]).value
-        assert err == (-9 if j == hit else 0), (what, j, err)
-        assert badb[j] == ((fl - 1) // BLOCK if j == hit else -1), (what, j)
-    a.check(a.expect(), what=what + " shard parse")
+
+class _SizedStep(Step):
+    def __init__(self, n, what=""):
+        self.n, self.what = n, what
+        self.raw = _raw(1, n, 9)[0]
+        self.framed, self.tail = oracle.sized_encode(self.raw.copy())
+
+    def image(self, dev, flip=None):
+        """The oracle's framed body in an arena of its own."""
+        a = Arena(dev, self.framed.size, 0, seed=28)
+        a.put(0, self.framed)
+        if flip is not None:
+            a.host[a.off + flip] ^= 1
+        a.upload()
+        return a
+
+
+class SizedEncode(_SizedStep):
+    def prepare(self, dev):
+        self.src = Arena(dev, self.n, 3, seed=27)
+        self.src.put(0, self.raw)
+        self.src.upload()
+        self.dst = Arena(dev, self.framed.size, 0, seed=28)
+        self.dst.upload()
+
+    def issue(self, enc):
+        self.w = L().gfrs_sized_encode(enc._ctx, vp(self.dst.ptr),
+                                       vp(self.src.ptr), self.n, BLOCK)
+
+    def check(self, enc):
+        sync(enc)
+        assert self.w == self.framed.size, (self.what, self.w)
+        want = self.dst.expect()
+        self.dst.put(0, self.framed, want)
+        self.dst.check(want, what=self.what + " sized encode")
+        self.src.check(self.src.expect(),
+                       what=self.what + " sized encode source")
+
+
+class SizedVerify(_SizedStep):
+    """corrupt=True flips the last payload byte of the last frame."""
+
+    def __init__(self, n, corrupt=False, what=""):
+        super().__init__(n, what)
+        self.last = self.framed.size - self.tail - 5 if corrupt else None
+
+    def prepare(self, dev):
+        self.a = self.image(dev, self.last)
+        self.badb = ctypes.c_int64(7)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_sized_verify(enc._ctx, vp(self.a.ptr),
+                                        self.framed.size, self.tail, BLOCK,
+                                        ctypes.byref(self.badb))
+
+    def check(self, enc):
+        ok(self.rc, self.what + " sized verify")
+        sync(enc)
+        want = -1 if self.last is None else self.last // BLOCK
+        assert self.badb.value == want, (self.what, self.badb.value)
+        self.a.check(self.a.expect(), what=self.what + " sized verify")
+
+
+class SizedDecode(_SizedStep):
+    def prepare(self, dev):
+        self.a = self.image(dev)
+        self.out = Arena(dev, self.n, 0, seed=29)
+        self.out.upload()
+
+    def issue(self, enc):
+        self.w = L().gfrs_sized_decode(enc._ctx, vp(self.out.ptr),
+                                       vp(self.a.ptr), self.framed.size,
+                                       self.tail, BLOCK)
+
+    def check(self, enc):
+        sync(enc)
+        assert self.w == self.n, (self.what, self.w)
+        want = self.out.expect()
+        self.out.put(0, self.raw, want)
+        self.out.check(want, what=self.what + " sized decode")
+        self.a.check(self.a.expect(), what=self.what + " sized decode source")
 
 
 def run_sized(dev, enc, n, what=""):
     """rpc2 sized coder: encode, verify (clean + corrupt), decode."""
-    raw = _raw(1, n, 9)[0]
-    want_f, tail = oracle.sized_encode(raw.copy())
-    src = Arena(dev, n, 3, seed=27)
-    src.put(0, raw)
-    src.upload()
-    dst = Arena(dev, want_f.size, 0, seed=28)
-    dst.upload()
-    w = L().gfrs_sized_encode(enc._ctx, vp(dst.ptr), vp(src.ptr), n, BLOCK)
-    assert w == want_f.size, (what, w)
-    want = dst.expect()
-    dst.put(0, want_f, want)
-    dst.check(want, what=what + " sized encode")
-    src.check(src.expect(), what=what + " sized encode source")
-    badb = ctypes.c_int64(7)
-    ok(L().gfrs_sized_verify(enc._ctx, vp(dst.ptr), want_f.size, tail, BLOCK,
-                             ctypes.byref(badb)), what + " sized verify")
-    assert badb.value == -1, (what, badb.value)
-    out = Arena(dev, n, 0, seed=29)
-    out.upload()
-    w = L().gfrs_sized_decode(enc._ctx, vp(out.ptr), vp(dst.ptr),
-                              want_f.size, tail, BLOCK)
-    assert w == n, (what, w)
-    want = out.expect()
-    out.put(0, raw, want)
-    out.check(want, what=what + " sized decode")
-    # corrupt the last payload byte of the last frame
-    last = want_f.size - tail - 5
-    dst.host[:] = dst.dev.cpu().numpy()
-    dst.host[dst.off + last] ^= 1
-    dst.upload()
-    ok(L().gfrs_sized_verify(enc._ctx, vp(dst.ptr), want_f.size, tail, BLOCK,
-                             ctypes.byref(badb)), what + " sized verify")
-    assert badb.value == last // BLOCK, (what, badb.value)
+    for step in (SizedEncode(n, what), SizedVerify(n, what=what),
+                 SizedDecode(n, what), SizedVerify(n, True, what)):
+        step.run(dev, enc)
 
 
-def run_encode_frame(dev, t, ref, pad=0, delta=0, extra=0, what="",
-                     composed=False):
+# ---- fused encode+frame, repair ------------------------------------------------
+
+class EncodeFrameBatch(_StripeStep):
     """gfrs_encode_frame_batch on a padded/offset source arena; every image
     row equals the oracle framing, source + all padding untouched.
     composed=True: the shape takes the documented encode_batch +
     crc32b_encode_batch composition, which also materialises the parity in
     `base`."""
-    enc = encoder(t)
-    ns, total, slen = ref.shape
-    lay = Stripes(ns, total, slen, pad)
-    src = Arena(dev, lay.nbytes, delta, seed=1)
-    # parity regions of the source stay random: the fused path must not
-    # read or write them
-    load_stripes(src, lay, ref, skip=range(t.N, total))
-    src.upload()
-    rows = Rows(ns * total, enc_size(slen), extra)
-    dst = Arena(dev, rows.nbytes, 4 if extra else 0, seed=2)
-    dst.upload()
-    rc = L().gfrs_encode_frame_batch(enc._ctx, vp(dst.ptr), rows.stride,
-                                     vp(src.ptr), slen, lay.stride, ns, BLOCK)
-    ok(rc, what)
-    sync(enc)
-    want = dst.expect()
-    for s in range(ns):
-        for i in range(total):
-            dst.put(rows.off(s * total + i),
-                    oracle.crc32b_encode(ref[s, i].copy()), want)
-    dst.check(want, what=what + " images")
-    src.check(want_like(src, lay, ref, range(t.N, total) if composed else ()),
-              what=what + " source")
+    blocking = False
+
+    def __init__(self, t, ref, pad=0, delta=0, extra=0, composed=False,
+                 what=""):
+        super().__init__(t, ref, pad, delta, 1, what)
+        self.extra, self.composed = extra, composed
+
+    def prepare(self, dev):
+        par = range(self.t.N, self.total)
+        # parity regions of the source stay random: the fused path must not
+        # read or write them
+        self.src = self.arena(dev, skip=par)
+        self.src.upload()
+        self.rows = rows = Rows(self.ns * self.total, enc_size(self.slen),
+                                self.extra)
+        self.dst = Arena(dev, rows.nbytes, 4 if self.extra else 0, seed=2)
+        self.dst.upload()
+        self.want = self.dst.expect()
+        for s in range(self.ns):
+            for i in range(self.total):
+                self.dst.put(rows.off(s * self.total + i),
+                             oracle.crc32b_encode(self.ref[s, i].copy()),
+                             self.want)
+        self.want_src = want_like(self.src, self.lay, self.ref,
+                                  par if self.composed else ())
+
+    def issue(self, enc):
+        self.rc = L().gfrs_encode_frame_batch(
+            enc._ctx, vp(self.dst.ptr), self.rows.stride, vp(self.src.ptr),
+            self.slen, self.lay.stride, self.ns, BLOCK)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        self.dst.check(self.want, what=self.what + " images")
+        self.src.check(self.want_src, what=self.what + " source")
+
+
+def run_encode_frame(dev, t, ref, pad=0, delta=0, extra=0, what="",
+                     composed=False):
+    EncodeFrameBatch(t, ref, pad, delta, extra, composed, what).run(
+        dev, encoder(t))
+
+
+class RepairBatch(_StripeStep):
+    """gfrs_repair_batch: images equal oracle.shard_write of the original
+    shards in the caller's column order; `base` untouched outside the bad
+    shards' regions.  corrupt = (stripe, shard, byte, mask) is applied to
+    a surviving shard; fails = the failed-stripe list after check().
+    Both paths synchronize for the fail words; the legacy path (m + l > 4)
+    then still queues one shard_write_batch per lost column and returns
+    with the last one's work queued."""
+
+    def __init__(self, t, ref, bad, pad=0, delta=0, extra=0, corrupt=None,
+                 what=""):
+        super().__init__(t, ref, pad, delta, 3, what)
+        self.bad, self.extra, self.corrupt = list(bad), extra, corrupt
+
+    def prepare(self, dev):
+        nb = len(self.bad)
+        src = self.src = self.arena(dev, skip=self.bad)
+        if self.corrupt:
+            s, i, b, mask = self.corrupt
+            src.host[src.off + self.lay.off(s, i) + b] ^= mask
+        src.upload()
+        self.rows = Rows(self.ns * nb, disk_size(self.slen), self.extra)
+        self.dst = Arena(dev, self.rows.nbytes, 4 if self.extra else 0,
+                         seed=4)
+        self.dst.upload()
+        self.bids = [7000 + j for j in range(self.ns * nb)]
+        self.vuids = [0x1122334455 + j for j in range(self.ns * nb)]
+        self.args = (i32s(self.bad), u64s(self.bids), u64s(self.vuids))
+        self.bm = bitmap(self.ns)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_repair_batch(
+            enc._ctx, vp(self.src.ptr), self.slen, self.lay.stride, self.ns,
+            self.args[0], len(self.bad), vp(self.dst.ptr), self.rows.stride,
+            BLOCK, self.args[1], self.args[2], self.bm)
+
+    def check(self, enc):
+        ok(self.rc, self.what)
+        sync(enc)
+        nb, rows = len(self.bad), self.rows
+        fails = self.fails = bits(self.bm, self.ns)
+        want = self.dst.expect()
+        for s in range(self.ns):
+            if s in fails:
+                # failed stripes' images are written but their content is
+                # not defined by the (corrupt) inputs
+                continue
+            for b, idx in enumerate(self.bad):
+                j = s * nb + b
+                self.dst.put(rows.off(j),
+                             oracle.shard_write(self.ref[s, idx].copy(),
+                                                bid=self.bids[j],
+                                                vuid=self.vuids[j]), want)
+        unspec = [(rows.off(s * nb + b), rows.row_len)
+                  for s in fails for b in range(nb)]
+        self.dst.check(want, unspec, what=self.what + " images")
+        self.src.check(self.src.expect(),
+                       [(self.lay.off(s, i), self.slen)
+                        for s in range(self.ns) for i in self.bad],
+                       what=self.what + " base")
 
 
 def run_repair(dev, t, ref, bad, pad=0, delta=0, extra=0, corrupt=None,
                what=""):
-    """gfrs_repair_batch: images equal oracle.shard_write of the original
-    shards in the caller's column order; `base` untouched outside the bad
-    shards' regions.  corrupt = (stripe, shard, byte, mask) is applied to
-    a surviving shard; returns the failed-stripe list."""
-    enc = encoder(t)
-    ns, total, slen = ref.shape
-    nb = len(bad)
-    lay = Stripes(ns, total, slen, pad)
-    src = Arena(dev, lay.nbytes, delta, seed=3)
-    load_stripes(src, lay, ref, skip=bad)
-    if corrupt:
-        s, i, b, mask = corrupt
-        src.host[src.off + lay.off(s, i) + b] ^= mask
-    src.upload()
-    rows = Rows(ns * nb, disk_size(slen), extra)
-    dst = Arena(dev, rows.nbytes, 4 if extra else 0, seed=4)
-    dst.upload()
-    bids = [7000 + j for j in range(ns * nb)]
-    vuids = [0x1122334455 + j for j in range(ns * nb)]
-    bm = bitmap(ns)
-    rc = L().gfrs_repair_batch(enc._ctx, vp(src.ptr), slen, lay.stride, ns,
-                               i32s(bad), nb, vp(dst.ptr), rows.stride,
-                               BLOCK, u64s(bids), u64s(vuids), bm)
-    ok(rc, what)
-    sync(enc)
-    fails = bits(bm, ns)
-    want = dst.expect()
-    for s in range(ns):
-        if s in fails:
-            # failed stripes' images are written but their content is not
-            # defined by the (corrupt) inputs
-            continue
-        for b, idx in enumerate(bad):
-            j = s * nb + b
-            dst.put(rows.off(j), oracle.shard_write(ref[s, idx].copy(),
-                                                    bid=bids[j],
-                                                    vuid=vuids[j]), want)
-    unspec = [(rows.off(s * nb + b), rows.row_len)
-              for s in fails for b in range(nb)]
-    dst.check(want, unspec, what=what + " images")
-    src.check(src.expect(),
-              [(lay.off(s, i), slen) for s in range(ns) for i in bad],
-              what=what + " base")
-    return fails
+    """One RepairBatch step; returns the failed-stripe list."""
+    return RepairBatch(t, ref, bad, pad, delta, extra, corrupt, what).run(
+        dev, encoder(t)).fails
+
+
+# ---- single-stripe calls: pointer tables and GFRS_MEM_HOST ---------------------
+
+MEM_DEVICE, MEM_HOST = runtime.MEM_DEVICE, runtime.MEM_HOST
+
+
+class _PtrStep(Step):
+    """All shards of stripe 0 of `ref` as views at odd, non-contiguous
+    offsets of one arena - device memory and a pointer table, or, with
+    host=True, host memory and GFRS_MEM_HOST (the engine stages the
+    stripe)."""
+
+    def __init__(self, t, ref, host=False, seed=30, what=""):
+        self.t, self.ref, self.host, self.seed = t, ref, host, seed
+        self.slen = ref.shape[2]
+        self.total = t.total
+        self.memloc = MEM_HOST if host else MEM_DEVICE
+        self.what = "%s%s" % (what, " (host)" if host else "")
+
+    def arena(self, dev, skip=(), extra_shards=0):
+        gap = self.slen + 3
+        n = self.total + extra_shards
+        a = (HostArena if self.host else Arena)(dev, n * gap, 1,
+                                                seed=self.seed)
+        self.offs = [i * gap for i in range(n)]
+        for i in range(self.total):
+            if i not in skip:
+                a.put(self.offs[i], self.ref[0, i])
+        return a
+
+    def table(self, idx):
+        return (ctypes.c_void_p * len(idx))(*[self.a.ptr + self.offs[i]
+                                              for i in idx])
+
+    def filled(self, shards, src=None):
+        want = self.a.expect()
+        for i in shards:
+            self.a.put(self.offs[i], (src or self.ref[0])[i], want)
+        return want
+
+
+class Encode(_PtrStep):
+    def prepare(self, dev):
+        par = range(self.t.N, self.total)
+        self.a = self.arena(dev, skip=par)
+        self.a.upload()
+        self.ptrs = self.table(range(self.total))
+        self.want = self.filled(par)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_encode(enc._ctx, self.ptrs, self.slen, self.total,
+                                  self.memloc)
+
+    def check(self, enc):
+        ok(self.rc, self.what + " gfrs_encode")
+        sync(enc)
+        self.a.check(self.want, what=self.what + " gfrs_encode")
+
+
+class Verify(_PtrStep):
+    """flip=True: one bit in the last byte of data shard 3."""
+
+    def __init__(self, t, ref, host=False, flip=False, seed=31, what=""):
+        super().__init__(t, ref, host, seed, what)
+        self.flip = flip
+
+    def prepare(self, dev):
+        a = self.a = self.arena(dev)
+        if self.flip:
+            a.host[a.off + self.offs[3] + self.slen - 1] ^= 2
+        a.upload()
+        self.ptrs = self.table(range(self.total))
+        self.okv = ctypes.c_int(-1)
+
+    def issue(self, enc):
+        self.rc = L().gfrs_verify(enc._ctx, self.ptrs, self.slen, self.total,
+                                  self.memloc, ctypes.byref(self.okv))
+
+    def check(self, enc):
+        ok(self.rc, self.what + " gfrs_verify")
+        sync(enc)
+        assert self.okv.value == (0 if self.flip else 1), \
+            (self.what, self.okv.value)
+        self.a.check(self.a.expect(), what=self.what + " gfrs_verify")
+
+
+class Reconstruct(_PtrStep):
+    def __init__(self, t, ref, host=False, bad=(8, 0), data_only=0, seed=32,
+                 what=""):
+        super().__init__(t, ref, host, seed, what)
+        self.bad, self.data_only = list(bad), data_only
+
+    def prepare(self, dev):
+        self.a = self.arena(dev, skip=self.bad)
+        self.a.upload()
+        self.ptrs = self.table(range(self.total))
+        self.badv = i32s(self.bad)
+        self.want = self.filled([i for i in self.bad
+                                 if not self.data_only or i < self.t.N])
+
+    def issue(self, enc):
+        self.rc = L().gfrs_reconstruct(enc._ctx, self.ptrs, self.slen,
+                                       self.total, self.memloc, self.badv,
+                                       len(self.bad), self.data_only)
+
+    def check(self, enc):
+        what = "%s gfrs_reconstruct data_only=%d" % (self.what,
+                                                      self.data_only)
+        ok(self.rc, what)
+        sync(enc)
+        self.a.check(self.want, what=what)
+
+
+class EncodeIdx(Step):
+    """gfrs_encode_idx of every data shard in `idxs` into zeroed parity, for
+    each stripe of `ref` in turn: call k accumulates into another stripe's
+    parity buffers than call k - 1, so len(ref) accumulations run
+    interleaved.  The parity of a stripe ends as the oracle's encode of its
+    data with every shard outside `idxs` taken as zero (all of them: the
+    oracle's parity)."""
+
+    def __init__(self, t, ref, idxs=None, seed=33, what=""):
+        self.t, self.ref, self.seed = t, ref, seed
+        self.ns, self.total, self.slen = ref.shape
+        self.idxs = list(range(t.N) if idxs is None else idxs)
+        self.what = what + " gfrs_encode_idx"
+
+    def prepare(self, dev):
+        t, gap = self.t, self.slen + 3
+        a = self.a = Arena(dev, self.ns * self.total * gap, 1, seed=self.seed)
+        want_par = []
+        for s in range(self.ns):
+            sh = [self.ref[s, i].copy() if i in self.idxs
+                  else np.zeros(self.slen, np.uint8)
+                  for i in range(self.total)]
+            oracle.rs_encode(t.N, t.M, sh)
+            want_par.append(sh)
+            for i in range(self.total):
+                a.put(self.off(s, i), self.ref[s, i] if i < t.N
+                      else np.zeros(self.slen, np.uint8))
+        a.upload()
+        self.want = a.expect()
+        for s in range(self.ns):
+            for i in range(t.N, self.total):
+                a.put(self.off(s, i), want_par[s][i], self.want)
+        self.pptrs = [(ctypes.c_void_p * t.M)(
+            *[a.ptr + self.off(s, i) for i in range(t.N, self.total)])
+            for s in range(self.ns)]
+        self.rcs = []
+
+    def off(self, s, i):
+        return (s * self.total + i) * (self.slen + 3)
+
+    def issue(self, enc):
+        f, ctx, a = L().gfrs_encode_idx, enc._ctx, self.a
+        for i in self.idxs:
+            for s in range(self.ns):
+                self.rcs.append(f(ctx, vp(a.ptr + self.off(s, i)), i,
+                                  self.pptrs[s], self.slen, self.t.M))
+
+    def check(self, enc):
+        for rc in self.rcs:
+            ok(rc, self.what)
+        sync(enc)
+        self.a.check(self.want, what=self.what)
+
+
+class UpdateIdx(_PtrStep):
+    """Replace data shard `idx`: the parity equals a fresh encode."""
+
+    def __init__(self, t, ref, idx=2, seed=34, what=""):
+        super().__init__(t, ref, False, seed, what)
+        self.idx = idx
+
+    def prepare(self, dev):
+        t = self.t
+        par = range(t.N, self.total)
+        self.a = self.arena(dev, extra_shards=1)
+        new = np.random.default_rng(77).integers(0, 256, self.slen,
+                                                 dtype=np.uint8)
+        self.a.put(self.offs[self.total], new)
+        self.a.upload()
+        self.pptrs = self.table(par)
+        sh = [self.ref[0, i].copy() for i in range(self.total)]
+        sh[self.idx] = new.copy()
+        oracle.rs_encode(t.N, t.M, sh)
+        self.want = self.filled(par, sh)
+
+    def issue(self, enc):
+        a = self.a
+        self.rc = L().gfrs_update_idx(
+            enc._ctx, vp(a.ptr + self.offs[self.idx]),
+            vp(a.ptr + self.offs[self.total]), self.idx, self.pptrs,
+            self.slen, self.t.M)
+
+    def check(self, enc):
+        ok(self.rc, self.what + " gfrs_update_idx")
+        sync(enc)
+        self.a.check(self.want, what=self.what + " gfrs_update_idx")
+
+
+# ---- the four queues -----------------------------------------------------------
+
+class QueueCall(Step):
+    """One queue call through the load / call / check of its helper module
+    (_repairq, _repairimgq, _encq or _readq) and a queue that module builds
+    by name."""
+
+    def __init__(self, module, name, what=""):
+        self.module, self.name = module, name
+        self.what = "%s %s %s" % (what, module, name)
+
+    def prepare(self, dev):
+        import importlib
+        self.m = importlib.import_module(self.module)
+        self.q = self.m.build(self.name)
+        loaded = self.m.load(self.q, dev)
+        self.arenas = loaded if isinstance(loaded, tuple) else (loaded,)
+
+    def issue(self, enc):
+        self.out = self.m.call(enc, *self.arenas, self.q)
+
+    def check(self, enc):
+        m, q, out, what = self.m, self.q, self.out, self.what
+        ok(out if isinstance(out, int) else out[0], what)
+        sync(enc)
+        if self.module == "_repairq":
+            want, fails, unspec = m.wanted(q, self.arenas[0])
+            assert out[1] == fails, (what, out[1], fails)
+            self.arenas[0].check(want, unspec, what=what)
+        elif self.module == "_encq":
+            m.check(q, *self.arenas, what)
+        else:
+            m.check(q, *self.arenas, out[1], what)
+
+

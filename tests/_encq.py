@@ -151,6 +151,10 @@ def build(name):
         return EQueue(name, V.get_tactic("EC6P6"),
                       [17, 4097, 65533, 1024, 16, 65597, 1, 131064, 16383,
                        2048, 4096, 8209])
+    if name == "seq_small":
+        # a step of tests/test_gpu_sequences.py: small and frame class
+        return EQueue(name, V.get_tactic("EC6P3"),
+                      [1000, 4093, 70001, 17, 4097])
     raise KeyError(name)
 
 

@@ -200,6 +200,11 @@ def build(name):
         pats = [[], [16], [0, 12], [14, 15], [3]]
         return GQueue(name, V.get_tactic("EC13P4"), pats,
                       _specs([1, 17, 4096, 65533, 131065], 5, 2, 1))
+    if name == "seq_small":
+        # a step of tests/test_gpu_sequences.py: one and two frames
+        pats = [[], [1], [0, 5], [7]]
+        return GQueue(name, V.get_tactic("EC6P3"), pats,
+                      _specs([1000, 4093, 70001], 4))
     if name.startswith("corrupt_"):
         return _corrupt(name)
     raise KeyError(name)

@@ -154,6 +154,10 @@ def build(name):
         return RQueue(Q.Queue(name, "EC6P3L3", pats,
                               _interleaved(lens, 4, 14),
                               cols=list(range(n + m, n + m + l))))
+    if name == "seq_small":
+        # a step of tests/test_gpu_sequences.py: small and frame class
+        return RQueue(Q.Queue(name, "EC6P3", [[1], [0, 5], [8, 1]],
+                              _interleaved([1000, 4093, 70001], 3, 6)))
     raise KeyError(name)
 
 

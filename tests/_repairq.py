@@ -146,6 +146,10 @@ def build(name):
         return Queue(name, "EC6P3L3", pats,
                      _interleaved([33, 4097, 17], 5, 10),
                      cols=list(range(n + m, n + m + l)))
+    if name == "seq_small":
+        # a step of tests/test_gpu_sequences.py: six short jobs
+        return Queue(name, "EC6P3", [[1], [0, 5], [7]],
+                     _interleaved([1000, 4093, 33], 3, 6))
     raise KeyError(name)
 
 

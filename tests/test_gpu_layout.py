@@ -6,16 +6,14 @@ Every call runs inside a guarded arena (tests/_arena.py): declared outputs
 are compared bit-exactly with the CPU oracle and every other byte of the
 arena (guards, padding, inputs) must come back unchanged.
 """
-import ctypes
 import itertools
 
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import _arena as A  # noqa: E402
-from _arena import L, Arena, Rows, Stripes, oracle, vp  # noqa: E402
+from _arena import L, Arena, Rows, Stripes, vp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -224,89 +222,22 @@ def test_shard_image_batch_layout(dev, t63, slen, extra):
 
 # ---- pointer-table single-stripe calls ---------------------------------------
 
-def _ptr_arena(dev, t, slen, ref, skip=(), extra_shards=0, seed=30):
-    """All shards of one stripe as views at odd, non-contiguous offsets."""
-    gap = slen + 3
-    n = t.total + extra_shards
-    a = Arena(dev, n * gap, 1, seed=seed)
-    offs = [i * gap for i in range(n)]
-    for i in range(t.total):
-        if i not in skip:
-            a.put(offs[i], ref[0, i])
-    ptrs = (ctypes.c_void_p * t.total)(*[a.ptr + offs[i]
-                                         for i in range(t.total)])
-    return a, offs, ptrs
-
-
 def test_pointer_table_calls_layout(dev, t63):
+    """All shards of one stripe as views at odd, non-contiguous offsets
+    (the steps of tests/_arena.py, one at a time)."""
     t, enc = t63, A.encoder(t63)
-    slen = 4093
-    ref = A.ref_stripes(t, 1, slen, seed=5)
-    par = range(t.N, t.total)
-
-    # gfrs_encode
-    a, offs, ptrs = _ptr_arena(dev, t, slen, ref, skip=par)
-    a.upload()
-    A.ok(L().gfrs_encode(enc._ctx, ptrs, slen, t.total, 0), "encode")
-    want = a.expect()
-    for i in par:
-        a.put(offs[i], ref[0, i], want)
-    a.check(want, what="gfrs_encode")
-
-    # gfrs_verify: clean, then one bit in the last byte of a data shard
-    for flip in (False, True):
-        a, offs, ptrs = _ptr_arena(dev, t, slen, ref, seed=31)
-        if flip:
-            a.host[a.off + offs[3] + slen - 1] ^= 2
-        a.upload()
-        okv = ctypes.c_int(-1)
-        A.ok(L().gfrs_verify(enc._ctx, ptrs, slen, t.total, 0,
-                             ctypes.byref(okv)), "verify")
-        assert okv.value == (0 if flip else 1)
-        a.check(a.expect(), what="gfrs_verify")
-
-    # gfrs_reconstruct, full and data_only
-    bad = [8, 0]
-    for data_only in (0, 1):
-        a, offs, ptrs = _ptr_arena(dev, t, slen, ref, skip=bad, seed=32)
-        a.upload()
-        A.ok(L().gfrs_reconstruct(enc._ctx, ptrs, slen, t.total, 0,
-                                  A.i32s(bad), 2, data_only), "reconstruct")
-        want = a.expect()
-        for i in ([0] if data_only else bad):
-            a.put(offs[i], ref[0, i], want)
-        a.check(want, what="gfrs_reconstruct data_only=%d" % data_only)
-
-    # gfrs_encode_idx: accumulate every data shard into zeroed parity
-    a, offs, ptrs = _ptr_arena(dev, t, slen, ref, skip=par, seed=33)
-    for i in par:
-        a.put(offs[i], np.zeros(slen, np.uint8))
-    a.upload()
-    pptrs = (ctypes.c_void_p * t.M)(*[a.ptr + offs[i] for i in par])
-    for i in range(t.N):
-        A.ok(L().gfrs_encode_idx(enc._ctx, vp(a.ptr + offs[i]), i, pptrs,
-                                 slen, t.M), "encode_idx")
-    want = a.expect()
-    for i in par:
-        a.put(offs[i], ref[0, i], want)
-    a.check(want, what="gfrs_encode_idx")
-
-    # gfrs_update_idx: replace data shard 2, parity equals a fresh encode
-    a, offs, ptrs = _ptr_arena(dev, t, slen, ref, extra_shards=1, seed=34)
-    new = np.random.default_rng(77).integers(0, 256, slen, dtype=np.uint8)
-    a.put(offs[t.total], new)
-    a.upload()
-    pptrs = (ctypes.c_void_p * t.M)(*[a.ptr + offs[i] for i in par])
-    A.ok(L().gfrs_update_idx(enc._ctx, vp(a.ptr + offs[2]),
-                             vp(a.ptr + offs[t.total]), 2, pptrs, slen, t.M),
-         "update_idx")
-    sh = [ref[0, i].copy() for i in range(t.total)]
-    sh[2] = new.copy()
-    oracle.rs_encode(t.N, t.M, sh)
-    want = a.expect()
-    for i in par:
-        a.put(offs[i], sh[i], want)
-    a.check(want, what="gfrs_update_idx")
+    ref = A.ref_stripes(t, 1, 4093, seed=5)
+    steps = [A.Encode(t, ref),
+             # clean, then one bit in the last byte of a data shard
+             A.Verify(t, ref, flip=False), A.Verify(t, ref, flip=True),
+             A.Reconstruct(t, ref, bad=[8, 0], data_only=0),
+             A.Reconstruct(t, ref, bad=[8, 0], data_only=1),
+             # accumulate every data shard into zeroed parity
+             A.EncodeIdx(t, ref),
+             # replace data shard 2, parity equals a fresh encode
+             A.UpdateIdx(t, ref, idx=2)]
+    for step in steps:
+        step.run(dev, enc)
 
 
 # ---- detection in the byte-tail paths, wide fail bitmaps -------------------
