@@ -199,6 +199,29 @@ void launch_rs_read_frame_queue(uint8_t *out, uint64_t framed,
                                 int kmax, int r, uint32_t *fail,
                                 hipStream_t s);
 
+/* Shard read queue: one bucket of the shard-read schedule (gfrs_plan.h).  An
+ * item reads the frames its range [from, to) touches of its image,
+ *   payload of frame f at chunk + item.img + 32 + f * 65536 + 4,
+ * writes the computed CRC of the frame at walk position w to fcrc[w] (fcrc
+ * already offset by the bucket's frame_base), lowers bad[item.job] to f
+ * when it differs from the stored word (bad preset to -1, compared unsigned),
+ * and - store = true - writes bytes [from, to) of the payload at
+ * out + item.out.  frame_prefix holds the nitems+1 exclusive prefix sums of
+ * touched frames, total_frames its last entry. */
+void launch_shard_read_frame_queue(uint8_t *out, uint64_t chunk,
+                                   const gfrs_sitem *items,
+                                   const uint64_t *frame_prefix,
+                                   uint32_t nitems, uint64_t total_frames,
+                                   bool store, uint32_t *fcrc, int64_t *bad,
+                                   hipStream_t s);
+/* ... and its results, one wave per job after the frame buckets: header bits
+ * and fields, BODY_CRC from bad[j], and for FOOTER jobs the fold of the job's
+ * fcrc words from fcrc[job_frame[j]] on and the two footer bits. */
+void launch_shard_head_queue(uint64_t chunk, const gfrs_sjob *jobs,
+                             const uint64_t *job_frame, const uint32_t *fcrc,
+                             const int64_t *bad, gfrs_sresult *results,
+                             int njobs, hipStream_t s);
+
 /* EncodeIdx-style accumulate apply (reedsolomon.go:631-668):
  * out[r] ^= coeff[r]*in for one input shard. */
 void launch_rs_apply_xor(const uint64_t *ptrs, int nptr,

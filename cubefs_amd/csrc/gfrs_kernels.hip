@@ -5505,6 +5505,306 @@ void launch_shard_parse(const uint8_t *img, size_t stride, int64_t raw_size,
                      stride, raw_size, block_len, nshards, out);
 }
 
+/* ---- shard read queue: verify and unframe the disk images of a chunk ---- */
+
+/* The read direction over disk images.  The walk is rs_read_frame_queue_k's:
+ * a contiguous frame range per block, one binary search then a forward walk
+ * over the prefix sums of TOUCHED frames, scalar item loads, every pointer
+ * rebuilt from the item; frame f of the walk is frame from / 65532 + f of the
+ * image, whose body starts 32 bytes in.  The frame is crc32b_verify_reg_k's:
+ * per 16 KiB pass a lane Horner-chains its four 16-byte pieces through the
+ * register CRC (crc16_reg / shift4k) and folds by its position operator - the
+ * same operators, the same partial-frame rule - and the ragged tail bytes
+ * take one lane each.  The pass terms stay in a register, so a frame costs
+ * one wave reduction.  No GF tables, no descriptor, no MAC.
+ * Lane 0 writes the computed CRC to fcrc[walk index] and lowers
+ * bad[item.job] to f when the stored 4-byte LE word differs.
+ * STORE adds the read kernel's clipped stores (store_clip16 / store_clip_tail
+ * and the byte path of the ragged tail): what was loaded is what is stored,
+ * only inside [from, to).  The STORE = false build has no global store but
+ * the fcrc word and the atomic.
+ * No lane leaves the frame loop early; no load leaves the touched frames of
+ * the item's image; no store leaves the item's declared bytes. */
+template <bool STORE, int WPS>
+__global__ __launch_bounds__(CRC_BLOCKT, WPS) void shard_read_frame_queue_k(
+    uint8_t *__restrict__ out, uint64_t chunk,
+    const gfrs_sitem *__restrict__ items,
+    const uint64_t *__restrict__ frame_prefix, uint32_t nitems,
+    uint64_t total_frames, uint32_t *__restrict__ fcrc,
+    unsigned long long *__restrict__ bad) {
+  constexpr int EF_PASS = 16384;
+  constexpr int EF_PASSES = 4;
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+  constexpr uint32_t INV16K = 0x479933FCu;
+
+  const uint64_t per_blk = (total_frames + gridDim.x - 1) / gridDim.x;
+  const uint64_t f_lo = uint64_t(blockIdx.x) * per_blk;
+  const uint64_t f_hi =
+      f_lo + per_blk < total_frames ? f_lo + per_blk : total_frames;
+  if (f_lo >= f_hi) return; /* whole block, before any barrier */
+
+  __shared__ __attribute__((aligned(16))) uint32_t tab[8][256];
+  __shared__ uint32_t stab[4][256];
+  __shared__ uint32_t red[4];
+  __shared__ uint32_t x8tab[16];
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift4k[0][0])[i];
+  if (threadIdx.x == 0) {
+    uint32_t v = 0x80000000u;
+    for (int j = 0; j < 16; j++) {
+      x8tab[j] = v;
+      v = gf2_mulmod_d(v, g_pow8[0]);
+    }
+  }
+  const int lane16i = int(threadIdx.x) * 16;
+  const uint32_t op_pA =
+      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16i + 16)));
+  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
+  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
+  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  const uint32_t it_full =
+      gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
+  __syncthreads();
+
+  /* largest it with frame_prefix[it] <= f_lo (frame_prefix[0] == 0) */
+  uint32_t it = 0;
+  for (uint32_t hi = nitems; hi - it > 1;) {
+    const uint32_t mid = it + (hi - it) / 2;
+    if (frame_prefix[mid] <= f_lo)
+      it = mid;
+    else
+      hi = mid;
+  }
+
+  for (uint64_t fr = f_lo; fr < f_hi; fr++) {
+    while (frame_prefix[it + 1] <= fr) it++; /* it + 1 <= nitems */
+    const gfrs_sitem item = items[it];
+    /* frame f of the image: the item's first touched frame + its walk index.
+     * Everything below is 32-bit and relative to the frame: payload bytes,
+     * and [lo, hi), the frame positions the range covers (lo % 4 == 0) */
+    const int64_t f = int64_t(item.from / uint64_t(payload_full)) +
+                      int64_t(fr - frame_prefix[it]);
+    const int64_t p0 = f * payload_full;
+    const int payload = int(i64min(payload_full, int64_t(item.size) - p0));
+    const int64_t slo = int64_t(item.from) - p0;
+    const int64_t shi = int64_t(item.to) - p0;
+    const int lo = slo > 0 ? int(slo) : 0;
+    const int hi = shi < int64_t(payload) ? int(shi) : payload;
+    const uint8_t *fb = as_global(chunk + item.img + 32) + f * block_len;
+    const uint8_t *pb = fb + CRC_LEN;
+    /* the address frame position 0 would have; dereferenced inside [lo, hi)
+     * only, and only by the STORE build */
+    uint8_t *rowf = reinterpret_cast<uint8_t *>(uint64_t(out) + item.out +
+                                                uint64_t(p0) - item.from);
+
+    uint32_t part = 0;
+#pragma unroll 1
+    for (int h = 0; h < EF_PASSES; h++) {
+      const int r0 = h * EF_PASS;
+      const int rbi = payload - r0 < EF_PASS ? payload - r0 : EF_PASS;
+      if (rbi <= 0) break; /* block-uniform */
+      const bool inside = lo <= r0 && r0 + rbi <= hi; /* block-uniform */
+
+      uint4 v[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        v[i] = off + 16 <= rbi
+                   ? *reinterpret_cast<const uint4 *>(pb + r0 + off)
+                   : uint4{0, 0, 0, 0};
+      }
+
+      uint32_t op = h == 0   ? op_pA
+                    : h == 1 ? op_pB
+                    : h == 2 ? op_pC
+                             : op_pD;
+      if (h == EF_PASSES - 1 && threadIdx.x == 255)
+        op = shift4k(op, stab); /* lane 255's last pass has 3 pieces */
+      if (payload != int(payload_full)) {
+        int np = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (i * 4096 + lane16i + 16 <= rbi) np = i + 1;
+        const int end = np ? r0 + (np - 1) * 4096 + lane16i + 16 : r0;
+        op = x8n_d(uint64_t(payload - end));
+      }
+
+      uint32_t t = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        if (off + 16 <= rbi) t = shift4k(t, stab) ^ crc16_reg(v[i], tab);
+      }
+      part ^= t ? gf2_mulmod_d(op, t) : 0;
+
+      if (STORE) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int off = i * 4096 + lane16i;
+          if (off + 16 <= rbi)
+            store_clip16(rowf, r0 + off, lo, hi, inside, v[i]);
+        }
+        if (!inside) store_clip_tail(rowf, r0, rbi & ~15, hi, v);
+      }
+      if (rbi & 15) { /* ragged tail of the frame: one lane per byte */
+        const int p = (rbi & ~15) + int(threadIdx.x);
+        if (p < rbi) {
+          const uint8_t x = pb[r0 + p];
+          part ^= gf2_mulmod_d(x8tab[rbi - 1 - p], tab[0][x]);
+          const int q = r0 + p;
+          if (STORE && q >= lo && q < hi) rowf[q] = x;
+        }
+      }
+    }
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) part ^= __shfl_xor(part, sh, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t itv =
+          payload == int(payload_full)
+              ? it_full
+              : gf2_mulmod_d(x8n_d(uint64_t(payload)), 0xFFFFFFFFu);
+      const uint32_t crc = ~(itv ^ red[0] ^ red[1] ^ red[2] ^ red[3]);
+      fcrc[fr] = crc;
+      const uint32_t want = uint32_t(fb[0]) | (uint32_t(fb[1]) << 8) |
+                            (uint32_t(fb[2]) << 16) | (uint32_t(fb[3]) << 24);
+      if (want != crc)
+        atomicMin(&bad[item.job], static_cast<unsigned long long>(f));
+    }
+    __syncthreads(); /* red is the next frame's too */
+  }
+}
+
+void launch_shard_read_frame_queue(uint8_t *out, uint64_t chunk,
+                                   const gfrs_sitem *items,
+                                   const uint64_t *frame_prefix,
+                                   uint32_t nitems, uint64_t total_frames,
+                                   bool store, uint32_t *fcrc, int64_t *bad,
+                                   hipStream_t s) {
+  if (nitems == 0 || total_frames == 0) return;
+  /* the cap of the other frame queues, read on every launch: GFRS_CRC_GRID
+   * forces the multi-frame walk at tiny shapes */
+  const uint64_t cap = uint64_t(env_grid("GFRS_CRC_GRID", 16384));
+  const int grid = int(total_frames < cap ? total_frames : cap);
+  /* waves per SIMD: 8, the verify kernel's; GFRS_SRD_WAVES = 4 or 8 overrides
+   * it and, like GFRS_RD_WAVES, is read on every launch, so a test can run
+   * both builds */
+  const char *we = getenv("GFRS_SRD_WAVES");
+  const int wv = we ? atoi(we) : 0;
+  unsigned long long *ubad = reinterpret_cast<unsigned long long *>(bad);
+#define GFRS_SRD_GO(ST, W)                                                  \
+  hipLaunchKernelGGL((shard_read_frame_queue_k<ST, W>), dim3(grid),         \
+                     dim3(CRC_BLOCKT), 0, s, out, chunk, items,             \
+                     frame_prefix, nitems, total_frames, fcrc, ubad)
+  if (store) {
+    if (wv == 4) GFRS_SRD_GO(true, 4);
+    else GFRS_SRD_GO(true, 8);
+  } else {
+    if (wv == 4) GFRS_SRD_GO(false, 4);
+    else GFRS_SRD_GO(false, 8);
+  }
+#undef GFRS_SRD_GO
+}
+
+/* One wave per job, after the frame buckets on the same stream: parse the
+ * 32-byte header (shard.go:278-305) into the three header bits and the stored
+ * fields, take BODY_CRC from bad[j], and for FOOTER jobs fold the job's
+ * computed frame CRCs into the CRC of the whole payload by
+ * shard_finalize_queue_k's rule - the operator of a full frame once, another
+ * only for the last frame - and compare the footer.  Geometry follows the
+ * job's size, never the header's. */
+__global__ void shard_head_queue_k(uint64_t chunk,
+                                   const gfrs_sjob *__restrict__ jobs,
+                                   const uint64_t *__restrict__ job_frame,
+                                   const uint32_t *__restrict__ fcrc,
+                                   const int64_t *__restrict__ bad,
+                                   gfrs_sresult *__restrict__ results,
+                                   int njobs) {
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+  const int j = blockIdx.x * (blockDim.x / 64) + (threadIdx.x / 64);
+  const int lane = threadIdx.x & 63;
+  if (j >= njobs) return; /* whole wave */
+  /* every lane does the wave-uniform work below; lane 0 writes the result */
+  const gfrs_sjob jb = jobs[j];
+  const uint8_t *img = as_global(chunk + jb.img_off);
+  uint32_t status = 0;
+  if (!(img[4] == 0xab && img[5] == 0xcd && img[6] == 0xef && img[7] == 0xcc))
+    status |= GFRS_SHARD_HDR_MAGIC;
+  uint32_t hcrc = 0xFFFFFFFFu;
+  for (int i = 4; i < 32; i++)
+    hcrc = g_crc_tab4[0][(hcrc ^ img[i]) & 0xFF] ^ (hcrc >> 8);
+  hcrc = ~hcrc;
+  const uint32_t want_h = (uint32_t(img[0]) << 24) | (uint32_t(img[1]) << 16) |
+                          (uint32_t(img[2]) << 8) | uint32_t(img[3]);
+  if (want_h != hcrc) status |= GFRS_SHARD_HDR_CRC;
+  uint64_t bid = 0, vuid = 0;
+  for (int i = 0; i < 8; i++) bid = (bid << 8) | img[8 + i];
+  for (int i = 0; i < 8; i++) vuid = (vuid << 8) | img[16 + i];
+  const uint64_t size = (uint64_t(img[24]) << 24) | (uint64_t(img[25]) << 16) |
+                        (uint64_t(img[26]) << 8) | uint64_t(img[27]);
+  if (bid != jb.bid || vuid != jb.vuid || size != jb.size)
+    status |= GFRS_SHARD_HDR_MISMATCH;
+  const int64_t bb = bad[j];
+  if (bb != -1) status |= GFRS_SHARD_BODY_CRC;
+  uint32_t crc = 0;
+  if (jb.flags & GFRS_SJOB_FOOTER) {
+    const int64_t raw_size = int64_t(jb.size);
+    const int64_t nframes = (raw_size + payload_full - 1) / payload_full;
+    const uint32_t *fc = fcrc + job_frame[j];
+    const uint32_t op_full = x8n_d(uint64_t(payload_full));
+    int64_t remain = raw_size;
+    /* the fold is serial, its loads are not: 64 words per wave load */
+    for (int64_t f0 = 0; f0 < nframes; f0 += 64) {
+      const uint32_t mine = f0 + lane < nframes ? fc[f0 + lane] : 0;
+      const int nf = int(nframes - f0 < 64 ? nframes - f0 : 64);
+      for (int i = 0; i < nf; i++) {
+        const uint32_t fcv = __shfl(mine, i, 64);
+        const int64_t plen = remain < payload_full ? remain : payload_full;
+        if (f0 + i == 0) {
+          crc = fcv;
+        } else {
+          const uint32_t op =
+              plen == payload_full ? op_full : x8n_d(uint64_t(plen));
+          crc = gf2_mulmod_d(op, crc) ^ fcv;
+        }
+        remain -= plen;
+      }
+    }
+    const uint8_t *ftr = img + 32 + (raw_size + CRC_LEN * nframes);
+    if (!(ftr[0] == 0xcc && ftr[1] == 0xef && ftr[2] == 0xcd &&
+          ftr[3] == 0xab))
+      status |= GFRS_SHARD_FTR_MAGIC;
+    const uint32_t want_f = (uint32_t(ftr[4]) << 24) |
+                            (uint32_t(ftr[5]) << 16) |
+                            (uint32_t(ftr[6]) << 8) | uint32_t(ftr[7]);
+    if (want_f != crc) status |= GFRS_SHARD_FTR_CRC;
+  }
+  gfrs_sresult r;
+  r.status = status;
+  r.crc = crc;
+  r.bad_block = bb;
+  r.bid = bid;
+  r.vuid = vuid;
+  r.size = size;
+  if (lane == 0) results[j] = r;
+}
+
+void launch_shard_head_queue(uint64_t chunk, const gfrs_sjob *jobs,
+                             const uint64_t *job_frame, const uint32_t *fcrc,
+                             const int64_t *bad, gfrs_sresult *results,
+                             int njobs, hipStream_t s) {
+  if (njobs <= 0) return;
+  const int wps = 4; /* waves per block */
+  const int blocks = (njobs + wps - 1) / wps;
+  hipLaunchKernelGGL(shard_head_queue_k, dim3(blocks), dim3(wps * 64), 0, s,
+                     chunk, jobs, job_frame, fcrc, bad, results, njobs);
+}
+
 /* Host-side one-time init of the device CRC tables (g_crc_tab4, g_pow8)
  * for the CURRENT device.  Called by gfrs_host.cpp under its device mutex. */
 int crc_device_init_current(void) {

@@ -342,6 +342,46 @@ int read_schedule(const Code &c, const gfrs_gjob *jobs, int njobs,
                   const ReadPattern *pats, int npat, uint64_t out_addr,
                   ReadSchedule *out);
 
+/* ---- the shard read queue (gfrs_shard_read_queue) ----
+ * Verify and unframe the disk images of one chunk.  There is no coding plan:
+ * the schedule only splits the jobs into the two builds of the frame kernel,
+ * storing jobs first, then NO_OUT jobs, each bucket in caller order with the
+ * count+1 exclusive prefix sums of the frames its items touch.  The computed
+ * CRC of the frame at walk position w of bucket b is kept at
+ * frame_base(b) + w of the context's scratch, job_frame[j] being the place of
+ * job j's first touched frame there (the header kernel folds a FOOTER job's
+ * words from it). */
+struct ShardReadBucket {
+  int no_out = 0;
+  size_t first = 0, count = 0; /* items[first, first+count) */
+  size_t prefix = 0; /* its count+1 frame prefix sums start here
+                        (= first + bucket index) */
+  uint64_t frame_base = 0; /* frames of the buckets before it */
+};
+
+struct ShardReadSchedule {
+  std::vector<gfrs_sitem> items;      /* both buckets' items, back to back */
+  std::vector<uint64_t> frame_prefix; /* exclusive prefix sums of the frames
+                                         TOUCHED by each item's range */
+  std::vector<ShardReadBucket> buckets; /* storing, then NO_OUT */
+  std::vector<uint64_t> job_frame;    /* njobs entries, caller order */
+  uint64_t total_frames = 0;
+};
+
+/* frames [first, last] of an image that the range touches */
+inline uint64_t shard_first_frame(const gfrs_sjob &j) {
+  return j.from / REPAIR_PAYLOAD;
+}
+inline uint64_t shard_last_frame(const gfrs_sjob &j) {
+  return (j.to - 1) / REPAIR_PAYLOAD;
+}
+
+/* Job validation (gfrs.h, shard-read-queue contract; out_addr = the address
+ * of out, for the alignment rule, have_out = it is not NULL) and the
+ * schedule.  block_len goes through encode_queue_block_check. */
+int shard_read_schedule(const gfrs_sjob *jobs, int njobs, uint64_t out_addr,
+                        bool have_out, ShardReadSchedule *out);
+
 }  // namespace gfrs
 
 #endif

@@ -201,6 +201,61 @@ class GBucket(ctypes.Structure):
     ]
 
 
+SJOB_NO_OUT, SJOB_FOOTER = 1, 2
+SHARD_HDR_MAGIC, SHARD_HDR_CRC, SHARD_HDR_MISMATCH = 1, 2, 4
+SHARD_BODY_CRC, SHARD_FTR_MAGIC, SHARD_FTR_CRC = 8, 16, 32
+
+
+class SJob(ctypes.Structure):
+    """gfrs_sjob: one job of a shard read queue."""
+    _fields_ = [
+        ("img_off", ctypes.c_uint64),
+        ("size", ctypes.c_uint64),
+        ("bid", ctypes.c_uint64),
+        ("vuid", ctypes.c_uint64),
+        ("from_", ctypes.c_uint64),
+        ("to", ctypes.c_uint64),
+        ("out_off", ctypes.c_uint64),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class SResult(ctypes.Structure):
+    """gfrs_sresult: what one job of a shard read queue gets back."""
+    _fields_ = [
+        ("status", ctypes.c_uint32),
+        ("crc", ctypes.c_uint32),
+        ("bad_block", ctypes.c_int64),
+        ("bid", ctypes.c_uint64),
+        ("vuid", ctypes.c_uint64),
+        ("size", ctypes.c_uint64),
+    ]
+
+
+class SItem(ctypes.Structure):
+    """gfrs_sitem: one work item of a shard-read schedule."""
+    _fields_ = [
+        ("img", ctypes.c_uint64),
+        ("size", ctypes.c_uint64),
+        ("from_", ctypes.c_uint64),
+        ("to", ctypes.c_uint64),
+        ("out", ctypes.c_uint64),
+        ("job", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+    ]
+
+
+class SBucket(ctypes.Structure):
+    """gfrs_sbucket: one frame launch of a shard-read schedule."""
+    _fields_ = [
+        ("no_out", ctypes.c_int32),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -333,6 +388,13 @@ def lib():
             ctypes.POINTER(Tactic), ctypes.POINTER(GJob), ctypes.c_int, i32p,
             i32p, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(GItem),
             u64p, ip, ctypes.POINTER(GBucket), ip, i32p, i32p, i32p, ip]
+        L.gfrs_shard_read_queue.argtypes = [vp, vp, vp, ctypes.POINTER(SJob),
+                                            ctypes.c_int, i64,
+                                            ctypes.POINTER(SResult)]
+        L.gfrs_compute_shard_read_queue_schedule.argtypes = [
+            ctypes.POINTER(SJob), ctypes.c_int, i64, ctypes.c_int,
+            ctypes.POINTER(SItem), u64p, ip, ctypes.POINTER(SBucket), ip,
+            u64p]
         _lib = L
     return _lib
 

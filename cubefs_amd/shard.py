@@ -9,7 +9,8 @@ header CRCs — the payload crosses HBM exactly once.
 """
 import ctypes
 
-from .runtime import GfrsError, Tactic, check, lib
+from .runtime import (GfrsError, SJob, SResult, Tactic, check,  # noqa: F401
+                      lib, SJOB_FOOTER, SJOB_NO_OUT)
 
 HEADER_SIZE = 32
 FOOTER_SIZE = 8
@@ -65,6 +66,25 @@ class ShardCodec:
                         "size": meta[4 * j + 2], "err": err,
                         "bad_block": bad[j]})
         return out
+
+    def read_queue(self, out, chunk, jobs, block_len=DEFAULT_BLOCK):
+        """Verify and unframe many images of one chunk in one call
+        (gfrs_shard_read_queue).  chunk: flat uint8 device tensor holding the
+        images; out: flat uint8 device tensor, or None when every job carries
+        SJOB_NO_OUT; jobs: [(img_off, size, bid, vuid, from, to, out_off,
+        flags)].  Returns a list of dicts {status, crc, bad_block, bid, vuid,
+        size}, one per job in the caller's order."""
+        nj = len(jobs)
+        arr = (SJob * max(1, nj))()
+        for j, job in enumerate(jobs):
+            arr[j] = SJob(*job, 0)
+        res = (SResult * max(1, nj))()
+        check(lib().gfrs_shard_read_queue(
+            self._ctx, None if out is None else out.data_ptr(),
+            chunk.data_ptr(), arr, nj, block_len, res), "shard_read_queue")
+        return [{"status": r.status, "crc": r.crc, "bad_block": r.bad_block,
+                 "bid": r.bid, "vuid": r.vuid, "size": r.size}
+                for r in res[:nj]]
 
     def synchronize(self):
         check(lib().gfrs_synchronize(self._ctx), "synchronize")

@@ -600,6 +600,106 @@ int gfrs_read_queue(gfrs_ctx *ctx, void *out, const void *framed,
                     const int32_t *bad_off, int npat, int64_t block_len,
                     uint32_t *bad_shards /* njobs words */);
 
+/* ---- shard read queue (datainspect.go:197-283 inspectChunk / inspectShard,
+ * shards_decoder.go:48-295 batch read, datafile.go:410-445 + chunk.go:448-589
+ * shard GET: the loop over the bids of one chunk, in the read direction) ----
+ * gfrs_shard_parse_batch and gfrs_crc32b_decode as a queue over disk images
+ * of different sizes lying anywhere in one chunk: every job names one image
+ * (what gfrs_shard_write_batch / gfrs_repair_queue wrote), what the shard meta
+ * says its header must hold, and a range [from, to) of the raw shard.  It gets
+ * back a word of independent status bits, the first bad frame, the header
+ * fields as stored and - unless it carries GFRS_SJOB_NO_OUT, the inspect
+ * form - the range with the frame CRCs stripped.  GFRS_SJOB_FOOTER adds the
+ * footer check of a whole shard.  jobs and results are host memory, chunk and
+ * out device pointers; out may be NULL when every job carries NO_OUT.
+ *
+ * Shard-read-queue contract (pinned by tests/test_gpu_shard_read_queue.py):
+ *  - Per-job result.  The status bits are independent facts about the image
+ *    bytes, each set exactly when its fact holds (the cgo shim picks the
+ *    reference's precedence):
+ *      HDR_MAGIC     bytes 4..8 are not ab cd ef cc;
+ *      HDR_CRC       the big-endian word at 0 differs from the CRC32-IEEE of
+ *                    bytes 4..32;
+ *      HDR_MISMATCH  the stored bid, vuid or size differs from the job's;
+ *      BODY_CRC      a touched frame - from / 65532 through (to - 1) / 65532 -
+ *                    stores a CRC that differs from the CRC32-IEEE of its
+ *                    payload;
+ *      FTR_MAGIC     FOOTER jobs only: the footer magic is not cc ef cd ab;
+ *      FTR_CRC       FOOTER jobs only: the footer's big-endian CRC differs
+ *                    from `crc`.
+ *    bad_block is the lowest touched frame (index within the image) with a
+ *    CRC mismatch, or -1, as in gfrs_shard_parse_batch.  crc is computed from
+ *    the payload bytes that were read, not folded from the stored frame
+ *    words, so FTR_CRC is the comparison of compact.go:263.  Geometry follows
+ *    the job's size, never the header's (the reference reads by the meta's
+ *    size too).  For a job with from = 0, to = size and FOOTER, status == 0
+ *    exactly when gfrs_shard_parse_batch on that image alone reports err == 0
+ *    and the job's ids, and bad_block is that call's answer.
+ *  - Output.  A job without NO_OUT gets bytes [from, to) of the image's
+ *    payload at out + out_off, whatever its status: what was loaded is what
+ *    is stored.  A job with NO_OUT writes nothing and costs no store.
+ *  - Layout.  Sources need no alignment.  Only touched frames are read, and
+ *    they are read whole; the 32-byte header is always read, the 8-byte
+ *    footer only for FOOTER jobs.  chunk is never written.  out + out_off and
+ *    from are multiples of 4 (raw positions and destination addresses stay
+ *    congruent).  In out only the declared to - from bytes of each job are
+ *    written.  Overlapping outputs are a caller error (not checked).
+ *  - Validation.  Everything is validated before the first launch, and any
+ *    error returns its code and writes nothing, neither in out nor in
+ *    results:
+ *      GFRS_ERR_INVALID_BLOCK for block_len <= 0 or not a multiple of 4096;
+ *      GFRS_ERR_UNSUPPORTED for any other block_len != 65536;
+ *      GFRS_ERR_SHARD_NO_DATA for size == 0;
+ *      GFRS_ERR_INVALID_SHARDS for njobs <= 0, size >= 2^32, reserved != 0,
+ *      unknown flag bits, from >= to, to > size, from % 4 != 0, FOOTER with
+ *      from != 0 or to != size, and on a job without NO_OUT a misaligned
+ *      out + out_off or out == NULL.
+ *  - Blocking.  The call blocks until the results are ready; it runs on the
+ *    context stream, takes the context mutex once and makes one upload of one
+ *    blob, one read-back and one sync.  It obeys the ordering contract above:
+ *    its upload waits out an id upload that an async gfrs_shard_write_batch
+ *    left queued.
+ *  - Launch bound.  At most 3 kernel launches whatever njobs is: the storing
+ *    jobs, the NO_OUT jobs, and one launch of one wave per job that parses
+ *    the headers and footers and writes the results.
+ *  - A job of at most 4096 bytes still occupies one workgroup (small jobs are
+ *    not packed together); the footer CRC of a FOOTER job is folded serially
+ *    over its frames. */
+enum { GFRS_SJOB_NO_OUT = 1, GFRS_SJOB_FOOTER = 2 };
+enum {
+  GFRS_SHARD_HDR_MAGIC = 1,    /* core.ErrShardHeaderMagic */
+  GFRS_SHARD_HDR_CRC = 2,      /* core.ErrShardHeaderCrc */
+  GFRS_SHARD_HDR_MISMATCH = 4, /* core.ErrShardHeaderNotMatch */
+  GFRS_SHARD_BODY_CRC = 8,     /* crc32block.ErrMismatchedCrc */
+  GFRS_SHARD_FTR_MAGIC = 16,
+  GFRS_SHARD_FTR_CRC = 32,
+};
+
+typedef struct gfrs_sjob {
+  uint64_t img_off;  /* image at chunk + img_off; no alignment needed */
+  uint64_t size;     /* raw shard size from the shard meta, 1 .. 2^32-1 */
+  uint64_t bid, vuid;/* what the meta says the header must hold */
+  uint64_t from, to; /* raw bytes [from, to) wanted; from % 4 == 0,
+                        from < to <= size */
+  uint64_t out_off;  /* those bytes at out + out_off (multiple of 4); ignored
+                        with NO_OUT */
+  uint32_t flags;    /* GFRS_SJOB_* */
+  uint32_t reserved; /* must be 0 */
+} gfrs_sjob;
+
+typedef struct gfrs_sresult {
+  uint32_t status;   /* OR of GFRS_SHARD_*; 0 = clean */
+  uint32_t crc;      /* FOOTER jobs: CRC32-IEEE of the size payload bytes in
+                        the image; else 0 */
+  int64_t bad_block; /* lowest touched frame (index within the image) whose
+                        CRC differs, or -1 */
+  uint64_t bid, vuid, size; /* header fields as stored, whatever the status */
+} gfrs_sresult;
+
+int gfrs_shard_read_queue(gfrs_ctx *ctx, void *out, const void *chunk,
+                          const gfrs_sjob *jobs, int njobs, int64_t block_len,
+                          gfrs_sresult *results /* njobs, host */);
+
 /* ---- ec.Buffer size math (buf.go:67-133) ---- */
 int gfrs_buffer_sizes(const gfrs_tactic *t, int64_t data_size,
                       int64_t *shard_size, int64_t *ec_data_size,
@@ -781,6 +881,35 @@ int gfrs_compute_read_queue_schedule(
     int64_t block_len, int item_cap, gfrs_gitem *items,
     uint64_t *frame_prefix, int *nitems, gfrs_gbucket *buckets, int *nbuckets,
     int32_t *pat_class, int32_t *pat_r, int32_t *slow_jobs, int *nslow);
+/* GPU-free: what gfrs_shard_read_queue would upload for a queue, with the same
+ * builder, so CPU tests can check it without a device.
+ *   Work items: one per job.  At most two buckets, in the fixed order storing
+ *   jobs (no_out = 0), then NO_OUT jobs (no_out = 1); bucket b owns
+ *   items[first, first+count), in caller order, and the count+1 exclusive
+ *   prefix sums of the TOUCHED frames of its items -
+ *   floor((to - 1) / 65532) - floor(from / 65532) + 1 - at
+ *   frame_prefix[first + b ...].
+ *   *total_frames is the sum over both buckets: the number of computed frame
+ *   CRCs the engine keeps in scratch (the storing bucket's first, then the
+ *   NO_OUT bucket's, each in walk order).
+ * items holds item_cap entries, frame_prefix item_cap + 2, buckets 2
+ * (GFRS_ERR_NOMEM when the schedule is larger).  Returns the validation codes
+ * of gfrs_shard_read_queue, taking out as 4-aligned and not NULL. */
+typedef struct gfrs_sitem {
+  uint64_t img;      /* byte offset in chunk of the image */
+  uint64_t size;     /* raw shard size */
+  uint64_t from, to;
+  uint64_t out;      /* byte offset in out of byte `from` */
+  int32_t job;       /* caller's index */
+  uint32_t flags;    /* of the job */
+} gfrs_sitem;
+typedef struct gfrs_sbucket {
+  int32_t no_out, first, count, reserved;
+} gfrs_sbucket;
+int gfrs_compute_shard_read_queue_schedule(
+    const gfrs_sjob *jobs, int njobs, int64_t block_len, int item_cap,
+    gfrs_sitem *items, uint64_t *frame_prefix, int *nitems,
+    gfrs_sbucket *buckets, int *nbuckets, uint64_t *total_frames);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);

@@ -46,6 +46,19 @@ and gfrs_read_queue, RS(12+4) (--only rs):
      with segments of 64 KiB or less: the queue vs a per-blob loop of the
      existing calls (12 decodes, reconstruct, slice copy).
 
+and gfrs_shard_read_queue over disk images (--only uvw), three interleaved
+medians of queue and yardstick each:
+
+ (u) inspect  512 images x 4 MiB, all NO_OUT | FOOTER: the queue vs ONE
+     gfrs_crc32b_verify_batch over the same bodies (the unchanged register-CRC
+     verify kernel).
+ (v) unframe  the same images, whole shard, storing: the queue vs ONE
+     gfrs_crc32b_decode of a single image of as many frames, the yardstick of
+     (r).
+ (w) mixed    the 4096-job size mix of (b), half the jobs inspecting, a
+     quarter reading the whole shard, a quarter a range of 64 KiB or less: the
+     queue vs one gfrs_shard_parse_batch per distinct size, a sync each.
+
 (a) and (d) run on random data with encoded parity; the others on a zeroed buffer
 (a valid stripe: zero parity), since the kernels' work does not depend on
 the data.  One JSON line on stdout; --out also writes it to a file.
@@ -569,6 +582,182 @@ class ReadProbe:
         return res
 
 
+class ShardProbe:
+    """gfrs_shard_read_queue against the parent's kernels, on disk images of
+    zero shards written by gfrs_shard_write_batch (the kernels' work does not
+    depend on the data).  The images of one size lie back to back at the tight
+    4-aligned stride, sizes in ascending order, so that the same chunk also
+    serves one gfrs_shard_parse_batch / gfrs_crc32b_verify_batch per size."""
+
+    def __init__(self):
+        self.enc = ec.Encoder(codemode.get_tactic("EC6P3"))
+        self.L = runtime.lib()
+
+    def chunk(self, lens):
+        """-> (chunk tensor, {size: (first offset, stride, count)}, offsets in
+        the order of lens)."""
+        groups, at = {}, 0
+        for ln in sorted(set(lens)):
+            stride = (self.L.gfrs_shard_disk_size(ln, 65536) + 3) // 4 * 4
+            groups[ln] = (at, stride, lens.count(ln))
+            at += stride * lens.count(ln)
+        chunk = torch.empty(at, dtype=torch.uint8, device="cuda")
+        for ln, (first, stride, count) in groups.items():
+            raw = torch.zeros(ln, dtype=torch.uint8, device="cuda")
+            ids = (ctypes.c_uint64 * 1)(5), (ctypes.c_uint64 * 1)(9)
+            rc = self.L.gfrs_shard_write_batch(
+                self.enc._ctx, chunk.data_ptr() + first, stride,
+                raw.data_ptr(), ln, ln, 65536, ids[0], ids[1], 1)
+            assert rc == 0, rc
+            self.enc.synchronize()
+            rows = chunk[first:first + stride * count].view(count, stride)
+            if count > 1:
+                rows[1:].copy_(rows[0].clone().expand(count - 1, stride))
+        seen, offs = {ln: 0 for ln in groups}, []
+        for ln in lens:
+            first, stride, _ = groups[ln]
+            offs.append(first + stride * seen[ln])
+            seen[ln] += 1
+        torch.cuda.synchronize()
+        return chunk, groups, offs
+
+    def sjobs(self, specs):
+        """specs: (img_off, size, from, to, out_off, flags)."""
+        sj = (runtime.SJob * len(specs))()
+        for j, (off, ln, frm, to, out, flags) in enumerate(specs):
+            sj[j] = runtime.SJob(off, ln, 5, 9, frm, to, out, flags, 0)
+        return sj, (runtime.SResult * len(specs))()
+
+    def queue(self, out_ptr, chunk, sj, res, check=False):
+        rc = self.L.gfrs_shard_read_queue(self.enc._ctx, out_ptr,
+                                          chunk.data_ptr(), sj, len(sj),
+                                          65536, res)
+        assert rc == 0, rc
+        if check:       # once, outside the timed calls: 4096 results in Python
+            assert not any(r.status for r in res), "status"
+            assert all(r.bad_block == -1 and r.size == j.size
+                       for r, j in zip(res, sj)), "results"
+
+    @staticmethod
+    def three(res, yard, queue, reps):
+        queue(check=True)
+        for i in (1, 2, 3):
+            res["yardstick_%d" % i] = timed(yard, reps)
+            res["queue_%d" % i] = timed(queue, reps)
+        ys = [res["yardstick_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        qs = [res["queue_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        res["yardstick_medians_ms"], res["queue_medians_ms"] = ys, qs
+        res["yardstick_spread"] = round(max(ys) / min(ys) - 1, 4)
+        res["queue_over_yardstick"] = round(statistics.median(qs) /
+                                            statistics.median(ys), 4)
+        if "GFRS_SRD_WAVES" in os.environ:
+            res["GFRS_SRD_WAVES"] = os.environ["GFRS_SRD_WAVES"]
+        return res
+
+    def inspect(self, njobs, slen, reps):
+        """(u): every image NO_OUT | FOOTER vs ONE gfrs_crc32b_verify_batch
+        over the same bodies (the unchanged register-CRC verify kernel)."""
+        chunk, groups, offs = self.chunk([slen] * njobs)
+        first, stride, _ = groups[slen]
+        sj, sres = self.sjobs([(off, slen, 0, slen, 0, 3) for off in offs])
+        body = self.L.gfrs_crc32b_encode_size(slen, 65536)
+        bad = (ctypes.c_int64 * njobs)()
+
+        def yardstick():
+            rc = self.L.gfrs_crc32b_verify_batch(
+                self.enc._ctx, chunk.data_ptr() + first + 32, stride, body,
+                65536, njobs, bad)
+            assert rc == 0 and all(b == -1 for b in bad), rc
+
+        res = {"njobs": njobs, "shard_len": slen,
+               "moved_GB": round(njobs * body / 1e9, 3)}
+        return self.three(res, yardstick,
+                          lambda check=False: self.queue(None, chunk, sj, sres,
+                                                         check), reps)
+
+    def unframe(self, njobs, slen, reps):
+        """(v): the same images, whole shard, storing, vs ONE
+        gfrs_crc32b_decode of a single image of as many frames (the yardstick
+        of (r))."""
+        chunk, groups, offs = self.chunk([slen] * njobs)
+        sj, sres = self.sjobs([(off, slen, 0, slen, j * slen, 0)
+                               for j, off in enumerate(offs)])
+        dst = torch.empty(njobs * slen, dtype=torch.uint8, device="cuda")
+        nframes = njobs * slen // 65532
+        yard = torch.empty(nframes * 65536, dtype=torch.uint8, device="cuda")
+        first = groups[slen][0]
+        yard.view(nframes, 65536).copy_(chunk[first + 32:first + 32 + 65536])
+
+        def yardstick():
+            w = self.L.gfrs_crc32b_decode(self.enc._ctx, dst.data_ptr(),
+                                          yard.data_ptr(), yard.numel(), 65536)
+            assert w == nframes * 65532, w
+
+        res = {"njobs": njobs, "shard_len": slen,
+               "moved_GB": round(njobs * slen * 2 / 1e9, 3)}
+        return self.three(res, yardstick,
+                          lambda check=False: self.queue(
+                              dst.data_ptr(), chunk, sj, sres, check), reps)
+
+    def mixed(self, lens, reps):
+        """(w): half the jobs inspect (NO_OUT | FOOTER), a quarter read the
+        whole shard, a quarter a range of 64 KiB or less, vs one
+        gfrs_shard_parse_batch per distinct size (each with its sync), which
+        answers the inspect half's question for every image and hands back no
+        byte."""
+        rng = random.Random(13)
+        chunk, groups, offs = self.chunk(lens)
+        specs, out = [], 0
+        for off, ln in zip(offs, lens):
+            kind = rng.randrange(4)
+            if kind < 2:
+                specs.append((off, ln, 0, ln, 0, 3))
+                continue
+            if kind == 2:
+                frm, to = 0, ln
+            else:
+                sl = rng.choice([4 * KIB, 16 * KIB, 64 * KIB])
+                frm = 4 * rng.randrange((ln - sl) // 4 + 1)
+                to = frm + sl
+            specs.append((off, ln, frm, to, out, 2 if kind == 2 else 0))
+            out += (to - frm + 3) // 4 * 4
+        sj, sres = self.sjobs(specs)
+        dst = torch.empty(max(4, out), dtype=torch.uint8, device="cuda")
+        meta = (ctypes.c_uint64 * (4 * len(lens)))()
+        bad = (ctypes.c_int64 * len(lens))()
+
+        def per_size():
+            for ln, (first, stride, count) in groups.items():
+                rc = self.L.gfrs_shard_parse_batch(
+                    self.enc._ctx, chunk.data_ptr() + first, stride, ln,
+                    65536, meta, bad, count)
+                assert rc == 0 and meta[3] == 0, rc
+
+        res = {"njobs": len(lens), "chunk_bytes": chunk.numel(),
+               "out_bytes": dst.numel(), "sizes": len(groups),
+               "inspect_jobs": sum(1 for s in specs if s[5] == 3),
+               "ranged_jobs": sum(1 for s in specs if s[5] == 0)}
+        return self.three(res, per_size,
+                          lambda check=False: self.queue(
+                              dst.data_ptr(), chunk, sj, sres, check), reps)
+
+
+def shard_main(a, out):
+    p = ShardProbe()
+    if "u" in a.only:
+        out["u_shard_inspect"] = p.inspect(512 // a.scale, 4 * MIB, reps=7)
+        torch.cuda.empty_cache()
+    if "v" in a.only:
+        out["v_shard_unframe"] = p.unframe(512 // a.scale, 4 * MIB, reps=7)
+        torch.cuda.empty_cache()
+    if "w" in a.only:
+        rng = random.Random(7)               # the lengths of (b)
+        lens = [rng.choice([64 * KIB, MIB, 4 * MIB])
+                for _ in range(4096 // a.scale)]
+        out["w_shard_mixed"] = p.mixed(lens, reps=5)
+        torch.cuda.empty_cache()
+
+
 def read_main(a, out):
     p = ReadProbe()
     out["read_tactic"] = "EC12P4"
@@ -616,13 +805,15 @@ def main():
     ap.add_argument("--only", default="abcde",
                     help="which configurations to run, e.g. 'ac'; the "
                     "encode+frame queue's are 'fpghi' (p = f'), the read "
-                    "queue's 'rs'")
+                    "queue's 'rs', the shard read queue's 'uvw'")
     a = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "scale": a.scale}
     if set(a.only) & set("fpghi"):
         encode_main(a, out)
     if set(a.only) & set("rs"):
         read_main(a, out)
+    if set(a.only) & set("uvw"):
+        shard_main(a, out)
     if not set(a.only) & set("abcde"):
         line = json.dumps(out)
         print(line)
