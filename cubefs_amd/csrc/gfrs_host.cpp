@@ -825,6 +825,8 @@ int gfrs_encode(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
     seterr("encode: want %d shards, got %d", total, nshards);
     return GFRS_ERR_INVALID_SHARDS;
   }
+  /* checkShards (reedsolomon.go:1314-1318) */
+  if (shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
   /* foreground call: fan out over the stream-lane pool so concurrent
    * callers on one context overlap on the GPU (the reference shares one
    * encoder across ~100 goroutines, encoder.go:29) */
@@ -904,6 +906,7 @@ int gfrs_verify(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
   /* full set or one local stripe set (lrcencoder.go:94-99) */
   bool local_form = c->code.t.l > 0 && nshards == total / c->code.t.az_count;
   if (nshards != total && !local_form) return GFRS_ERR_INVALID_SHARDS;
+  if (shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
   Lane *L = c->pick_lane();
   std::unique_lock<std::mutex> lk(L ? L->mu : c->mu);
   StreamGuard g(c);
@@ -954,10 +957,6 @@ int gfrs_reconstruct(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
                      int nbad, int data_only) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
   const gfrs_tactic &t = c->code.t;
-  Lane *L = c->pick_lane();
-  std::unique_lock<std::mutex> lk(L ? L->mu : c->mu);
-  StreamGuard g(c);
-  const LaneView lv = L ? view_of(L) : view_of(c);
   int rc;
 
   if (t.m == 0) /* no parity: any missing shard is unrecoverable */
@@ -965,12 +964,17 @@ int gfrs_reconstruct(gfrs_ctx *ctx, void *const *shards, size_t shard_len,
   /* full set or, for LRC, a single local stripe (lrcencoder.go:147-153) */
   bool local_form = t.l > 0 && nshards == c->code.total / t.az_count;
   if (nshards != c->code.total && !local_form) return GFRS_ERR_INVALID_SHARDS;
+  if (shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
 
   std::vector<uint8_t> present(nshards, 1);
   for (int i = 0; i < nbad; i++) {
     if (bad_idx[i] < 0 || bad_idx[i] >= nshards) return GFRS_ERR_INVALID_SHARDS;
     present[bad_idx[i]] = 0;
   }
+  Lane *L = c->pick_lane();
+  std::unique_lock<std::mutex> lk(L ? L->mu : c->mu);
+  StreamGuard g(c);
+  const LaneView lv = L ? view_of(L) : view_of(c);
 
   /* host memory: stage the whole stripe contiguously, run strided */
   const bool host = memloc == GFRS_MEM_HOST;
@@ -1265,8 +1269,11 @@ int gfrs_shard_parse_batch(gfrs_ctx *ctx, const void *img, size_t stride,
 int gfrs_encode_idx(gfrs_ctx *ctx, const void *data_shard, int idx,
                     void *const *parity, size_t shard_len, int nparity) {
   auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
-  if (idx < 0 || idx >= c->code.t.n || nparity != c->code.t.m)
-    return GFRS_ERR_INVALID_SHARDS;
+  /* the reference's order (reedsolomon.go:632-647) */
+  if (nparity != c->code.t.m) return GFRS_ERR_TOO_FEW_SHARDS;
+  if (nparity == 0) return GFRS_OK; /* replicate: no parity rows, :635-637 */
+  if (idx < 0 || idx >= c->code.t.n) return GFRS_ERR_INVALID_SHARDS;
+  if (shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
   std::lock_guard<std::mutex> lk(c->mu);
   StreamGuard g(c);
   int rc;
@@ -1953,6 +1960,8 @@ int gfrs_shard_read_queue(gfrs_ctx *ctx, void *out, const void *chunk,
 int gfrs_update_idx(gfrs_ctx *ctx, const void *old_shard,
                     const void *new_shard, int idx, void *const *parity,
                     size_t shard_len, int nparity) {
+  /* the first pass validates for both: its checks depend on nothing the
+   * second pass is given differently, so a refused call has run neither */
   int rc = gfrs_encode_idx(ctx, old_shard, idx, parity, shard_len, nparity);
   if (rc != GFRS_OK) return rc;
   return gfrs_encode_idx(ctx, new_shard, idx, parity, shard_len, nparity);

@@ -93,6 +93,23 @@ class Encoder:
         arr = (ctypes.c_void_p * len(shards))(*[v[0] for v in views])
         return arr, ln, (MEM_DEVICE if dev else MEM_HOST)
 
+    def _idx_ptrs(self, data_shard, others, parity):
+        """Parity pointer table and shard length of an incremental-parity
+        call.  These calls take device pointers only, and every buffer has
+        the data shard's length (ErrShardSize, reedsolomon.go:641-647): a
+        shorter parity would be written past its end."""
+        views = [_shard_view(s) for s in (data_shard, *others, *parity)]
+        ln = views[0][1]
+        for p, n, d in views:
+            if not d:
+                raise GfrsError(-6, "incremental parity takes device shards")
+        for p, n, d in views:
+            if n != ln:
+                raise GfrsError(-3, "unequal shard sizes")
+        arr = (ctypes.c_void_p * len(parity))(
+            *[v[0] for v in views[1 + len(others):]])
+        return arr, ln
+
     # ---- the Encoder interface ----
 
     def encode(self, shards):
@@ -259,19 +276,14 @@ class Encoder:
     def encode_idx(self, data_shard, idx, parity):
         """EncodeIdx (reedsolomon.go:631): parity[r] ^= coeff[r][idx]*data.
         Parity must start zeroed; call once per data shard."""
-        t = self.tactic
-        views = [_shard_view(s) for s in parity]
-        arr = (ctypes.c_void_p * len(parity))(*[v[0] for v in views])
-        ln = _shard_view(data_shard)[1]
+        arr, ln = self._idx_ptrs(data_shard, (), parity)
         check(lib().gfrs_encode_idx(self._ctx, data_shard.data_ptr(), idx,
                                     arr, ln, len(parity)), "encode_idx")
 
     def update_idx(self, old_shard, new_shard, idx, parity):
         """Update (reedsolomon.go:676): patch parity for a replaced data
         shard: parity[r] ^= coeff[r][idx]*(old^new)."""
-        views = [_shard_view(s) for s in parity]
-        arr = (ctypes.c_void_p * len(parity))(*[v[0] for v in views])
-        ln = _shard_view(old_shard)[1]
+        arr, ln = self._idx_ptrs(old_shard, (new_shard,), parity)
         check(lib().gfrs_update_idx(self._ctx, old_shard.data_ptr(),
                                     new_shard.data_ptr(), idx, arr, ln,
                                     len(parity)), "update_idx")

@@ -133,7 +133,56 @@ int gfrs_synchronize(gfrs_ctx *ctx);
  * semantics: the caller owns the buffers on return).  The batch APIs
  * below are async on the ctx stream; synchronize with
  * gfrs_synchronize().  When the shards form one contiguous ec.Buffer
- * layout (buf.go:24-35) the pointer-table upload is skipped. */
+ * layout (buf.go:24-35) the pointer-table upload is skipped.
+ *
+ * Single-stripe contract (pinned by tests/test_gpu_single_stripe.py; it
+ * covers gfrs_encode_idx and gfrs_update_idx further down as well):
+ *  - Only declared outputs are written: the parities of gfrs_encode, the
+ *    shards listed in bad_idx of gfrs_reconstruct (with data_only the data
+ *    shards among them; a lost parity then keeps the caller's bytes), the m
+ *    global parities of gfrs_encode_idx / gfrs_update_idx (never a local
+ *    parity).  gfrs_verify writes *ok and nothing else.  Every input shard
+ *    and every byte between and around the shards stay as they were, for any
+ *    shard_len >= 1 and any alignment.  The contiguous and the pointer-table
+ *    form of gfrs_encode write the same bytes.
+ *  - A GFRS_MEM_HOST gfrs_reconstruct copies back only the shards it rebuilt;
+ *    the buffers of surviving shards are never written.
+ *  - An LRC context (l > 0) accepts two forms of gfrs_verify and
+ *    gfrs_reconstruct: the full set, nshards == n+m+l, where Verify checks
+ *    the global stripe and every local stripe and Reconstruct rebuilds global
+ *    shards from the global stripe and lost local parities from their AZ's
+ *    stripe; and one local stripe given on its own, nshards ==
+ *    (n+m+l) / az_count (lrcencoder.go:93-99,147-152), the shards of one AZ in
+ *    LocalStripeInAZ order, a plain RS((n+m)/az_count + l/az_count) stripe
+ *    with bad_idx counting positions in that list.  data_only has no meaning
+ *    in the local form (the reference's ReconstructData slices to n+m) and is
+ *    not part of the contract there.  gfrs_encode takes the full set only.
+ *  - Errors.  A refused call writes nothing (gfrs_verify leaves *ok alone)
+ *    and launches nothing; all but gfrs_reconstruct's
+ *    GFRS_ERR_TOO_FEW_SHARDS return before anything is staged or uploaded
+ *    either.  Checks run in the order listed:
+ *      gfrs_encode        nshards != n+m+l          GFRS_ERR_INVALID_SHARDS
+ *                         shard_len == 0            GFRS_ERR_SHARD_NO_DATA
+ *      gfrs_verify,       nshards neither n+m+l nor (l > 0) (n+m+l)/az_count
+ *      gfrs_reconstruct                             GFRS_ERR_INVALID_SHARDS
+ *                         shard_len == 0            GFRS_ERR_SHARD_NO_DATA
+ *      gfrs_reconstruct   a bad index outside [0, nshards)
+ *                                                   GFRS_ERR_INVALID_SHARDS
+ *                         more than m of the n+m global shards lost, with or
+ *                         without lost local parities (none of which is then
+ *                         written); local form: more than l/az_count losses
+ *                                                   GFRS_ERR_TOO_FEW_SHARDS
+ *                         nbad == 0, or data_only with only parities lost
+ *                                                   GFRS_OK, nothing written
+ *      gfrs_encode_idx,   nparity != m              GFRS_ERR_TOO_FEW_SHARDS
+ *      gfrs_update_idx    nparity == 0 (replicate)  GFRS_OK, nothing done,
+ *                                                   whatever idx is
+ *                         idx outside [0, n)        GFRS_ERR_INVALID_SHARDS
+ *                         shard_len == 0            GFRS_ERR_SHARD_NO_DATA
+ *    (reedsolomon.go:632-647, checkShards :1314-1318).  A replicate context
+ *    (m == 0) keeps its own answers: Encode and Verify are no-ops that check
+ *    nshards only, Reconstruct succeeds only when nothing is missing.  The
+ *    batch calls below are not part of this table. */
 
 /* Encoder.Encode (encoder.go:114 / lrcencoder.go:35): fills parity (and
  * local parity when l > 0) from the data shards. */
@@ -337,7 +386,10 @@ int gfrs_reconstruct_verify_queue(gfrs_ctx *ctx, void *base,
 /* ---- incremental parity (reedsolomon.go:631-668 EncodeIdx) ----
  * Adds data shard idx's contribution into the m parity shards:
  * parity[r] ^= coeff[r][idx]*data.  Parity must be zeroed before the
- * first call; each data shard delivered exactly once.  Device pointers. */
+ * first call; each data shard delivered exactly once.  Device pointers.
+ * Errors as in the single-stripe contract above; an idx outside [0, n) is
+ * the reference's ErrInvShardNum, which has no code of its own here and is
+ * reported as GFRS_ERR_INVALID_SHARDS. */
 int gfrs_encode_idx(gfrs_ctx *ctx, const void *data_shard, int idx,
                     void *const *parity, size_t shard_len, int nparity);
 

@@ -838,24 +838,35 @@ class _PtrStep(Step):
     """All shards of stripe 0 of `ref` as views at odd, non-contiguous
     offsets of one arena - device memory and a pointer table, or, with
     host=True, host memory and GFRS_MEM_HOST (the engine stages the
-    stripe)."""
+    stripe).
 
-    def __init__(self, t, ref, host=False, seed=30, what=""):
+    gap: distance between shard starts (default slen + 3; gap = slen is the
+    contiguous ec.Buffer layout, still at an odd base address).
+    members: global shard indices presented as an nshards = len(members)
+    call, e.g. one local stripe of an LRC tactic; every shard index of the
+    step (skip, bad, flipped shard) is then a position in that list, and
+    total, the call's shard count, is its length."""
+
+    def __init__(self, t, ref, host=False, seed=30, what="", gap=None,
+                 members=None):
         self.t, self.ref, self.host, self.seed = t, ref, host, seed
         self.slen = ref.shape[2]
-        self.total = t.total
+        self.members = list(range(t.total) if members is None else members)
+        self.total = len(self.members)
+        self.rows = ref[0, self.members]
+        self.gap = self.slen + 3 if gap is None else gap
         self.memloc = MEM_HOST if host else MEM_DEVICE
         self.what = "%s%s" % (what, " (host)" if host else "")
 
     def arena(self, dev, skip=(), extra_shards=0):
-        gap = self.slen + 3
+        gap = self.gap
         n = self.total + extra_shards
         a = (HostArena if self.host else Arena)(dev, n * gap, 1,
                                                 seed=self.seed)
         self.offs = [i * gap for i in range(n)]
         for i in range(self.total):
             if i not in skip:
-                a.put(self.offs[i], self.ref[0, i])
+                a.put(self.offs[i], self.rows[i])
         return a
 
     def table(self, idx):
@@ -865,7 +876,8 @@ class _PtrStep(Step):
     def filled(self, shards, src=None):
         want = self.a.expect()
         for i in shards:
-            self.a.put(self.offs[i], (src or self.ref[0])[i], want)
+            self.a.put(self.offs[i],
+                       (self.rows if src is None else src)[i], want)
         return want
 
 
@@ -888,16 +900,20 @@ class Encode(_PtrStep):
 
 
 class Verify(_PtrStep):
-    """flip=True: one bit in the last byte of data shard 3."""
+    """flip=True: one bit in byte `byte` (default: the last) of shard
+    `shard` (default: data shard 3)."""
 
-    def __init__(self, t, ref, host=False, flip=False, seed=31, what=""):
-        super().__init__(t, ref, host, seed, what)
-        self.flip = flip
+    def __init__(self, t, ref, host=False, flip=False, seed=31, what="",
+                 shard=3, byte=None, **kw):
+        super().__init__(t, ref, host, seed, what, **kw)
+        self.flip, self.shard = flip, shard
+        self.byte = self.slen - 1 if byte is None else byte
 
     def prepare(self, dev):
         a = self.a = self.arena(dev)
         if self.flip:
-            a.host[a.off + self.offs[3] + self.slen - 1] ^= 2
+            assert 0 <= self.byte < self.slen
+            a.host[a.off + self.offs[self.shard] + self.byte] ^= 2
         a.upload()
         self.ptrs = self.table(range(self.total))
         self.okv = ctypes.c_int(-1)
@@ -915,9 +931,13 @@ class Verify(_PtrStep):
 
 
 class Reconstruct(_PtrStep):
+    """`bad` is in the call's own index space: positions in `members` for a
+    local-stripe step.  The erased shards keep the arena's random fill, so a
+    shard the call must not rebuild (data_only) has to come back as it was."""
+
     def __init__(self, t, ref, host=False, bad=(8, 0), data_only=0, seed=32,
-                 what=""):
-        super().__init__(t, ref, host, seed, what)
+                 what="", **kw):
+        super().__init__(t, ref, host, seed, what, **kw)
         self.bad, self.data_only = list(bad), data_only
 
     def prepare(self, dev):
@@ -963,18 +983,21 @@ class EncodeIdx(Step):
             sh = [self.ref[s, i].copy() if i in self.idxs
                   else np.zeros(self.slen, np.uint8)
                   for i in range(self.total)]
+            sh = sh[:t.N + t.M]
             oracle.rs_encode(t.N, t.M, sh)
             want_par.append(sh)
+            # local parities (l > 0) are no part of the call: they lie in
+            # the arena as encoded and must come back untouched
             for i in range(self.total):
-                a.put(self.off(s, i), self.ref[s, i] if i < t.N
-                      else np.zeros(self.slen, np.uint8))
+                a.put(self.off(s, i), np.zeros(self.slen, np.uint8)
+                      if t.N <= i < t.N + t.M else self.ref[s, i])
         a.upload()
         self.want = a.expect()
         for s in range(self.ns):
-            for i in range(t.N, self.total):
+            for i in range(t.N, t.N + t.M):
                 a.put(self.off(s, i), want_par[s][i], self.want)
         self.pptrs = [(ctypes.c_void_p * t.M)(
-            *[a.ptr + self.off(s, i) for i in range(t.N, self.total)])
+            *[a.ptr + self.off(s, i) for i in range(t.N, t.N + t.M)])
             for s in range(self.ns)]
         self.rcs = []
 
@@ -996,22 +1019,28 @@ class EncodeIdx(Step):
 
 
 class UpdateIdx(_PtrStep):
-    """Replace data shard `idx`: the parity equals a fresh encode."""
+    """Replace data shard `idx`: the global parity equals a fresh encode;
+    local parities (l > 0) are no part of the call and stay.  same=True:
+    the new shard has the old one's content, so the parity must come back
+    unchanged."""
 
-    def __init__(self, t, ref, idx=2, seed=34, what=""):
+    def __init__(self, t, ref, idx=2, seed=34, what="", same=False):
         super().__init__(t, ref, False, seed, what)
-        self.idx = idx
+        self.idx, self.same = idx, same
 
     def prepare(self, dev):
         t = self.t
-        par = range(t.N, self.total)
+        par = range(t.N, t.N + t.M)
         self.a = self.arena(dev, extra_shards=1)
-        new = np.random.default_rng(77).integers(0, 256, self.slen,
-                                                 dtype=np.uint8)
+        if self.same:
+            new = self.ref[0, self.idx].copy()
+        else:
+            new = np.random.default_rng(77).integers(0, 256, self.slen,
+                                                     dtype=np.uint8)
         self.a.put(self.offs[self.total], new)
         self.a.upload()
         self.pptrs = self.table(par)
-        sh = [self.ref[0, i].copy() for i in range(self.total)]
+        sh = [self.ref[0, i].copy() for i in range(t.N + t.M)]
         sh[self.idx] = new.copy()
         oracle.rs_encode(t.N, t.M, sh)
         self.want = self.filled(par, sh)

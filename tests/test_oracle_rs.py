@@ -170,6 +170,39 @@ def test_local_stripe_layout(oracle):
     assert oracle.lrc_local_stripe(6, 10, 2, 2, 1) == [3, 4, 5, 11, 12, 13, 14, 15, 17]
 
 
+@pytest.mark.parametrize("n,m,l,az", [(12, 2, 2, 2), (6, 10, 2, 2),
+                                      (16, 20, 2, 2)],
+                         ids=["LRC12P2L2", "EC6P10L2", "EC16P20L2"])
+def test_local_stripe_is_an_rs_stripe(oracle, n, m, l, az):
+    """One local stripe given on its own (lrcencoder.go:93-99,147-152) is a
+    plain RS((n+m)/az + l/az) stripe: for every AZ, rs_reconstruct of each
+    single lost member - the local parity included - returns the bytes
+    lrc_encode produced, and rs_verify turns false for a one-bit flip in
+    each member.  This is the reference the GPU local-form tests use."""
+    slen = 333
+    rng = np.random.default_rng(n * 100 + m + 7)
+    shards = [rng.integers(0, 256, slen, dtype=np.uint8) for _ in range(n)] + \
+             [np.zeros(slen, np.uint8) for _ in range(m + l)]
+    oracle.lrc_encode(n, m, l, az, shards)
+    ln, lm = (n + m) // az, l // az
+    for a in range(az):
+        idx = oracle.lrc_local_stripe(n, m, l, az, a)
+        assert len(idx) == ln + lm == (n + m + l) // az
+        ref = [shards[i].copy() for i in idx]
+        assert oracle.rs_verify(ln, lm, [x.copy() for x in ref]), a
+        for j in range(len(idx)):
+            loc = [x.copy() for x in ref]
+            loc[j][:] = 0xEE
+            present = np.ones(len(idx), np.uint8)
+            present[j] = 0
+            assert oracle.rs_reconstruct(ln, lm, loc, present) == 0, (a, j)
+            for i in range(len(idx)):
+                assert np.array_equal(loc[i], ref[i]), (a, j, i)
+            flipped = [x.copy() for x in ref]
+            flipped[j][(j * 37) % slen] ^= 1 << (j % 8)
+            assert not oracle.rs_verify(ln, lm, flipped), (a, j)
+
+
 def test_buffer_sizes(oracle):
     """buf_test.go:45-174 semantics."""
     # 8 MiB data, EC6P3, min 2 KiB
