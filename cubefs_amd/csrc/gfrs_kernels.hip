@@ -771,6 +771,9 @@ __device__ uint32_t g_shift4k[4][256];
 __device__ uint32_t g_shift1k[4][256];
 /* and x^(8*8192): the 32-B-piece dual-aligned kernel's lane stride */
 __device__ uint32_t g_shift8k[4][256];
+/* and x^(8*13312): the aligned kernel's step from a lane's last piece of one
+ * pass to its first piece of the next (16384 - 3 * 1024 bytes) */
+__device__ uint32_t g_shift13k[4][256];
 
 /* x^(8*2^j) mod P, reflected domain — host-filled alongside the tables. */
 __device__ uint32_t g_pow8[40];
@@ -2247,7 +2250,7 @@ GFRS_DEV AlLd al_load(const uint8_t *sp, int r, int P, int nfull, int q0) {
                 : uint4{0, 0, 0, 0};
   }
   const int qe = q0 + 193; /* lane 63: the chunk after its piece 3 */
-  const bool em = (threadIdx.x & 63) == 63 && r > 0 &&
+  const bool em = (q0 & 63) == 63 /* lane 63: q0 = lane (mod 64) */ && r > 0 &&
                   (FULL || (qe <= nfull && 16 * qe - 4 - 4 * r < P));
   o.e = em ? *reinterpret_cast<const u32x3a *>(sp + 16 * qe)
            : u32x3a{0, 0, 0};
@@ -2271,6 +2274,10 @@ GFRS_DEV uint32_t al_rol1(uint32_t v) {
  * lane's position operator is ~40% of a unit's VALU work in the looped
  * compare/select form; as sign-extended bit masks it is ~6 VALU per bit */
 GFRS_DEV uint32_t al_mulmod(uint32_t a, uint32_t b) {
+  /* the operator is loop-invariant at every call site: without this the 32
+   * bit masks of `a` are hoisted out of the frame loop, where they hold 32
+   * VGPRs and 64 SGPRs for the whole kernel and spill */
+  asm volatile("" : "+v"(a));
   uint32_t prod = 0;
 #pragma unroll
   for (int i = 31; i >= 0; i--) {
@@ -2301,30 +2308,51 @@ GFRS_DEV uint32_t al_wave_xor(uint32_t x) {
                   __builtin_amdgcn_readlane(int(x), 48));
 }
 
-template <int R>
-GFRS_DEV void al_rot(uint4 (&d)[4], const AlLd &c) {
+/* piece I of a unit rotated into destination space.  It needs only v[I]
+ * and lane 0 of v[I+1], so each loaded piece dies as it is consumed. */
+template <int R, int I>
+GFRS_DEV uint4 al_rot1(const AlLd &c) {
+  const uint4 own = c.v[I];
+  uint32_t n[3] = {0, 0, 0};
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint4 own = c.v[i];
-    uint32_t n[3] = {0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < R; j++) {
-      const uint32_t ownj = j == 0 ? own.x : j == 1 ? own.y : own.z;
-      uint32_t edge;
-      if (i < 3) {
-        const uint4 nx = c.v[i < 3 ? i + 1 : 3];
-        edge = al_rol1(j == 0 ? nx.x : j == 1 ? nx.y : nx.z);
-      } else {
-        edge = j == 0 ? c.e.x : j == 1 ? c.e.y : c.e.z;
-      }
-      n[j] = al_shl1(edge, ownj);
+  for (int j = 0; j < R; j++) {
+    const uint32_t ownj = j == 0 ? own.x : j == 1 ? own.y : own.z;
+    uint32_t edge;
+    if (I < 3) {
+      const uint4 nx = c.v[I < 3 ? I + 1 : 3];
+      edge = al_rol1(j == 0 ? nx.x : j == 1 ? nx.y : nx.z);
+    } else {
+      edge = j == 0 ? c.e.x : j == 1 ? c.e.y : c.e.z;
     }
-    d[i] = R == 0   ? own
-           : R == 1 ? uint4{own.y, own.z, own.w, n[0]}
-           : R == 2 ? uint4{own.z, own.w, n[0], n[1]}
-                    : uint4{own.w, n[0], n[1], n[2]};
+    n[j] = al_shl1(edge, ownj);
+  }
+  return R == 0   ? own
+         : R == 1 ? uint4{own.y, own.z, own.w, n[0]}
+         : R == 2 ? uint4{own.z, own.w, n[0], n[1]}
+                  : uint4{own.w, n[0], n[1], n[2]};
+}
+
+/* the frame's rotation r is wave-uniform: one scalar branch per piece */
+template <int I>
+GFRS_DEV uint4 al_rot_piece(const AlLd &c, int r) {
+  switch (r) {
+    case 0: return al_rot1<0, I>(c);
+    case 1: return al_rot1<1, I>(c);
+    case 2: return al_rot1<2, I>(c);
+    default: return al_rot1<3, I>(c);
   }
 }
+
+/* pins a rotated piece in registers where the switch joins: left free, the
+ * compiler turns "dword r of the loaded piece" into an r-indexed read of a
+ * private array, and the loaded pieces go through scratch */
+GFRS_DEV void al_pin(uint4 &v) {
+  asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+}
+
+/* LDS bytes ahead of the running-CRC slab (the launch adds (k+m+1) KB for
+ * the slab and the coefficient tables) */
+constexpr int AL_LDS_FIXED = 12288 + EF_RED + 64 + 256 + 1024 + 256 + 4096;
 
 template <int GM, int WPS, int SKEL = 0, int ST = 0, int C0 = 0>
 __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
@@ -2336,7 +2364,9 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
   constexpr int payload_full = 65532;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   /* crc tables 8 KB | shift1k 4 KB | red slab | x8tab | tailb | tinyb |
-   * chunk-0 slab (16 x 16 B) | coefficient tables */
+   * chunk-0 slab (16 x 16 B) | shift13k 4 KB | running-CRC slab
+   * [k+GM][256] dwords and one more row, the lanes' fold operators |
+   * coefficient tables */
   uint32_t(*tab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem);
   uint32_t(*stab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem + 8192);
   uint32_t *red = reinterpret_cast<uint32_t *>(smem + 12288);
@@ -2345,11 +2375,18 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
   uint8_t *tinyb = smem + 12288 + EF_RED + 64 + 256; /* 16 x 64 */
   uint32_t *c0b =
       reinterpret_cast<uint32_t *>(smem + 12288 + EF_RED + 64 + 256 + 1024);
-  uint8_t *ctab = smem + 12288 + EF_RED + 64 + 256 + 1024 + 256;
+  uint32_t(*stab13)[256] = reinterpret_cast<uint32_t(*)[256]>(
+      smem + 12288 + EF_RED + 64 + 256 + 1024 + 256);
+  /* a full frame's running CRC per shard and lane, carried from pass to
+   * pass; lane-contiguous, so every access is conflict-free */
+  uint32_t *run0 = reinterpret_cast<uint32_t *>(smem + AL_LDS_FIXED);
+  uint8_t *ctab = smem + AL_LDS_FIXED + (k + GM + 1) * 1024;
   for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
     (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
   for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
     (&stab[0][0])[i] = (&g_shift1k[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab13[0][0])[i] = (&g_shift13k[0][0])[i];
   for (int i = threadIdx.x; i < GM * k * 2; i += CRC_BLOCKT)
     reinterpret_cast<uint4 *>(ctab)[i] =
         reinterpret_cast<const uint4 *>(tabs)[i];
@@ -2363,13 +2400,12 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
   const int tid = int(threadIdx.x);
   /* lane's piece-0 chunk within a pass: wave-contiguous map */
   const int ql0 = (tid >> 6) * 256 + (tid & 63);
-  /* full-frame fold operators: all four pieces are always valid, the
-   * suffix after the lane's last piece of pass 0 is 65536 - 16*(ql0+193) */
-  constexpr uint32_t INV16K = 0x479933FCu;
-  const uint32_t op_pA = x8n_d(uint64_t(65536 - 16 * (ql0 + 192 + 1)));
-  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
-  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
-  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  /* full-frame fold operator: a full frame's CRC is one Horner chain per
+   * lane and shard over all 16 pieces (1024 B apart within a pass, 13312 B
+   * from piece 3 of a pass to piece 0 of the next), folded once by the
+   * suffix after the lane's last piece of pass 3, 16384 - 16*(ql0+193).
+   * The operator waits in LDS: it is needed once per shard per frame */
+  run0[(k + GM) * 256 + tid] = x8n_d(uint64_t(16384 - 16 * (ql0 + 192 + 1)));
   const uint32_t it_full =
       gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
   __syncthreads();
@@ -2406,7 +2442,16 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
     const int64_t abase = p0 - 4 - 4 * r; /* shard offset of L_0 */
     const uint8_t *sbase = as_global(base + stripe * stripe_stride);
 
-    for (int j = threadIdx.x; j < 64; j += CRC_BLOCKT) red[j] = 0;
+    /* the lane ids are re-derived per frame behind an opaque copy: without
+     * it every lane mask and per-piece offset derived from them is hoisted
+     * out of the frame loop and held, mostly spilled, for the whole kernel */
+    int tidf = int(threadIdx.x);
+    asm volatile("" : "+v"(tidf));
+    const int tid = tidf;
+    const int ql0 = (tid >> 6) * 256 + (tid & 63);
+    uint32_t *run = run0 + tid;
+
+    if (tid < 64) red[tid] = 0;
     __syncthreads();
 
     /* the four passes; FULL (a whole 65532-B frame, the common case) drops
@@ -2415,19 +2460,20 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
     auto passes = [&](auto fullc) {
     constexpr bool FULL = decltype(fullc)::value;
     uint4 acc[GM][4];
+#pragma unroll 1
     for (int h = 0; h < 4; h++) {
       if (!FULL && 1024 * h >= ntot) break;
-      const int qp = 1024 * h + ql0; /* lane's piece-0 chunk */
+      int qp = 1024 * h + ql0; /* lane's piece-0 chunk */
+      /* ragged frames: keep the per-piece addresses and masks of this
+       * rare path from being set up, and spilled, at the top of every frame */
+      if (!FULL) asm volatile("" : "+v"(qp));
       const bool tail = !FULL && tb != 0 && (nfull >> 10) == h;
 #pragma unroll
       for (int rr = 0; rr < GM; rr++)
 #pragma unroll
         for (int i = 0; i < 4; i++) acc[rr][i] = uint4{0, 0, 0, 0};
 
-      uint32_t op = h == 0   ? op_pA
-                    : h == 1 ? op_pB
-                    : h == 2 ? op_pC
-                             : op_pD;
+      uint32_t op = 0; /* ragged and short frames fold every pass */
       if (!FULL) {
         int np = 0;
 #pragma unroll
@@ -2449,22 +2495,20 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
         const AlLd cur = nx;
         if (c + 1 < k)
           nx = al_load<FULL>(src + shard_len + abase, r, P, nfull, qp);
-        /* rotate into destination space: all lanes active here (DPP
-         * reads neighbour lanes), masked pieces carry zeros */
-        uint4 d[4];
-        switch (r) {
-          case 0: al_rot<0>(d, cur); break;
-          case 1: al_rot<1>(d, cur); break;
-          case 2: al_rot<2>(d, cur); break;
-          default: al_rot<3>(d, cur); break;
-        }
-        if (qp == 0) d[0].x = 0; /* header slot of chunk 0 */
+        /* a full frame continues the shard's chain from the previous pass
+         * (pass 0 starts it: a shifted zero is zero) */
         uint32_t t = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
+        if (FULL && SKEL != 1) t = shift4k(h ? run[c * 256] : 0u, stab13);
+        /* one piece at a time: rotate into destination space (all lanes
+         * active here, DPP reads neighbour lanes; masked pieces carry
+         * zeros), then MAC, store and CRC it */
+        auto piece = [&](auto ic) {
+          constexpr int i = decltype(ic)::value;
+          uint4 v = al_rot_piece<i>(cur, r);
+          al_pin(v);
+          if (i == 0 && qp == 0) v.x = 0; /* header slot of chunk 0 */
           const int q = qp + 64 * i;
           if (FULL || q < nfull) {
-            const uint4 v = d[i];
             if (SKEL != 1) {
 #pragma unroll
               for (int dd = 0; dd < 4; dd++)
@@ -2482,8 +2526,17 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
             } else {
               fstore16<ST>(fdst + 16 * q, v);
             }
-            if (SKEL != 1) t = shift4k(t, stab) ^ crc16_reg(v, tab);
+            if (SKEL != 1)
+              t = (FULL && i == 0 ? t : shift4k(t, stab)) ^ crc16_reg(v, tab);
           }
+        };
+        piece(std::integral_constant<int, 0>{});
+        piece(std::integral_constant<int, 1>{});
+        piece(std::integral_constant<int, 2>{});
+        piece(std::integral_constant<int, 3>{});
+        if (FULL) {
+          if (SKEL != 1) run[c * 256] = t;
+          continue;
         }
         uint32_t part = al_mulmod(op, t);
         if (tail) {
@@ -2519,6 +2572,8 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
         uint8_t *fdst =
             dst + (stripe * (k + GM) + k + rr) * dst_stride + f * block_len;
         uint32_t t = 0;
+        if (FULL && SKEL != 1)
+          t = shift4k(h ? run[(k + rr) * 256] : 0u, stab13);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int q = qp + 64 * i;
@@ -2536,8 +2591,13 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
             } else {
               fstore16<ST>(fdst + 16 * q, v);
             }
-            if (SKEL != 1) t = shift4k(t, stab) ^ crc16_reg(v, tab);
+            if (SKEL != 1)
+              t = (FULL && i == 0 ? t : shift4k(t, stab)) ^ crc16_reg(v, tab);
           }
+        }
+        if (FULL) {
+          if (SKEL != 1) run[(k + rr) * 256] = t;
+          continue;
         }
         uint32_t part = al_mulmod(op, t);
         if (SKEL != 1 && tail) {
@@ -2554,6 +2614,14 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
         }
         part = al_wave_xor(part);
         if ((tid & 63) == 0) red[(tid >> 6) * 16 + k + rr] ^= part;
+      }
+    }
+    if (FULL && SKEL != 1) {
+      /* one position fold per shard: each lane reads back its own chain */
+      const uint32_t op_pD = run[(k + GM) * 256];
+      for (int j = 0; j < k + GM; j++) {
+        const uint32_t part = al_wave_xor(al_mulmod(op_pD, run[j * 256]));
+        if ((tid & 63) == 0) red[(tid >> 6) * 16 + j] ^= part;
       }
     }
     };
@@ -2587,6 +2655,7 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
       const int64_t tp0 = (f + 1) * payload_full;
       if (j < k) {
         const uint8_t *sp = sbase + size_t(j) * shard_len + tp0;
+#pragma clang loop vectorize(disable) unroll(disable)
         for (int b = 0; b < tiny_len; b++) tinyb[j * 64 + b] = sp[b];
       }
       __syncthreads();
@@ -2594,12 +2663,14 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
         uint8_t *tb2 =
             dst + (stripe * (k + GM) + j) * dst_stride + (f + 1) * block_len;
         uint32_t cr = 0;
+#pragma clang loop vectorize(disable) unroll(disable)
         for (int b = 0; b < tiny_len; b++) {
           uint8_t x;
           if (j < k) {
             x = tinyb[j * 64 + b];
           } else {
             x = 0;
+#pragma clang loop vectorize(disable) unroll(disable)
             for (int c2 = 0; c2 < k; c2++)
               x ^= gfmul1_lin(ctab + size_t((j - k) * k + c2) * 32,
                               tinyb[c2 * 64 + b]);
@@ -4530,8 +4601,9 @@ void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
                   : (kAlAuto && al_ok && var_old == 76) ? 79
                                                         : var_old;
   if (var == 79) {
-    const int lds = 12288 + EF_RED + 64 + 256 + 1024 + 256 + m * k * 32;
-#define GFRS_AL_GO(G, SK, C)                                              \
+    const int lds =
+        AL_LDS_FIXED + (k + (m < 4 ? m : 4) + 1) * 1024 + m * k * 32;
+#define GFRS_AL_GO(G, SK, C)                                             \
   hipLaunchKernelGGL((rs_encode_frame_al_k<G, 3, SK, 0, C>), dim3(grid2), \
                      dim3(CRC_BLOCKT), lds, s, dst, dst_stride, base,     \
                      stripe_stride, shard_len, k, ltabs, total2, fps2,    \
@@ -5850,6 +5922,13 @@ int crc_device_init_current(void) {
     for (uint32_t b = 0; b < 256; b++)
       s4k[j][b] = mulmod(pow8[13], b << (8 * j)); /* x^(8*2^13) */
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_shift8k), s4k, sizeof(s4k)) != hipSuccess)
+    return -100;
+  /* 13312 = 2^13 + 2^12 + 2^10 */
+  const uint32_t x13k = mulmod(mulmod(pow8[13], pow8[12]), pow8[10]);
+  for (int j = 0; j < 4; j++)
+    for (uint32_t b = 0; b < 256; b++)
+      s4k[j][b] = mulmod(x13k, b << (8 * j));
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_shift13k), s4k, sizeof(s4k)) != hipSuccess)
     return -100;
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_crc_tab4), tab, sizeof(tab)) != hipSuccess)
     return -100;
