@@ -248,6 +248,8 @@ struct gfrs_ctx_impl {
                         their first-frame places and bad blocks of one call
                         (the uploaded blob), then the computed frame CRCs and
                         the results */
+  DevBuf shardwq_buf; /* shard write queue: the same, with the write queue's
+                         items and jobs */
   DevBuf read_scratch; /* read queue, slow jobs: one decoded stripe of the
                           touched frames; grown on demand, freed with the
                           context */
@@ -1953,6 +1955,78 @@ int gfrs_shard_read_queue(gfrs_ctx *ctx, void *out, const void *chunk,
                                                       is read until here */
   if (e != hipSuccess) return hip_fail("shard_read_queue launch", e);
   if (se != hipSuccess) return hip_fail("shard_read_queue sync", se);
+  memcpy(results, back.data(), nres);
+  return GFRS_OK;
+}
+
+/* The shard write queue: gfrs_shard_write_batch per job, over payloads of any
+ * size that are raw bytes or the body of an existing image, as one call.
+ * gfrs_plan.cpp validates the jobs and splits them into the raw and the
+ * SRC_IMAGE bucket; this function uploads one blob [work items | frame prefix
+ * sums | jobs | first-frame places | bad blocks preset to -1] through the
+ * pinned staging, issues the <= 2 frame buckets and the head launch, reads
+ * the results back and syncs once.  The computed frame CRCs and the results
+ * follow the blob in the same grow-only scratch. */
+int gfrs_shard_write_queue(gfrs_ctx *ctx, void *dst, const void *src,
+                           const gfrs_wjob *jobs, int njobs, int64_t block_len,
+                           gfrs_sresult *results) {
+  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+  int rc = encode_queue_block_check(block_len);
+  if (rc != GFRS_OK) return rc;
+  if (njobs <= 0 || !jobs || !results || !dst || !src)
+    return GFRS_ERR_INVALID_SHARDS;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+  ShardWriteSchedule sched;
+  rc = shard_write_schedule(jobs, njobs, (uint64_t)dst, &sched);
+  if (rc != GFRS_OK) return rc;
+
+  const size_t nj = size_t(njobs);
+  const size_t o_prefix = nj * sizeof(gfrs_witem);
+  const size_t o_jobs = o_prefix + sched.frame_prefix.size() * 8;
+  const size_t o_place = o_jobs + nj * sizeof(gfrs_wjob);
+  const size_t o_bad = o_place + nj * 8;
+  const size_t nblob = o_bad + nj * 8;
+  const size_t o_fcrc = nblob;
+  const size_t o_res = (o_fcrc + size_t(sched.total_frames) * 4 + 7) / 8 * 8;
+  const size_t nres = nj * sizeof(gfrs_sresult);
+  if ((rc = c->shardwq_buf.ensure(o_res + nres)) != GFRS_OK) return rc;
+  uint8_t *dq = (uint8_t *)c->shardwq_buf.p;
+  /* the staging an async gfrs_shard_write_batch may still upload its ids
+   * from: pin_for_write waits that copy out */
+  uint8_t *blob;
+  if ((rc = pin_for_write(view_of(c), nblob, &blob)) != GFRS_OK) return rc;
+  memcpy(blob, sched.items.data(), o_prefix);
+  memcpy(blob + o_prefix, sched.frame_prefix.data(), o_jobs - o_prefix);
+  memcpy(blob + o_jobs, jobs, o_place - o_jobs);
+  memcpy(blob + o_place, sched.job_frame.data(), o_bad - o_place);
+  memset(blob + o_bad, 0xFF, nblob - o_bad);
+
+  uint32_t *fcrc = (uint32_t *)(dq + o_fcrc);
+  int64_t *bad = (int64_t *)(dq + o_bad);
+  hipError_t e =
+      hipMemcpyAsync(dq, blob, nblob, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    for (const ShardWriteBucket &b : sched.buckets)
+      launch_shard_write_frame_queue(
+          (uint8_t *)dst, (uint64_t)src, (const gfrs_witem *)dq + b.first,
+          (const uint64_t *)(dq + o_prefix) + b.prefix, uint32_t(b.count),
+          sched.frame_prefix[b.prefix + b.count], b.src_image != 0,
+          fcrc + b.frame_base, bad, c->stream);
+    launch_shard_write_head_queue(
+        (uint8_t *)dst, (uint64_t)src, (const gfrs_wjob *)(dq + o_jobs),
+        (const uint64_t *)(dq + o_place), fcrc, bad,
+        (gfrs_sresult *)(dq + o_res), njobs, c->stream);
+    e = hipGetLastError();
+  }
+  std::vector<gfrs_sresult> back(nj);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(back.data(), dq + o_res, nres, hipMemcpyDeviceToHost,
+                       c->stream);
+  hipError_t se = hipStreamSynchronize(c->stream); /* the one sync; the blob
+                                                      is read until here */
+  if (e != hipSuccess) return hip_fail("shard_write_queue launch", e);
+  if (se != hipSuccess) return hip_fail("shard_write_queue sync", se);
   memcpy(results, back.data(), nres);
   return GFRS_OK;
 }

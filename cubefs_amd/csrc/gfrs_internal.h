@@ -222,6 +222,37 @@ void launch_shard_head_queue(uint64_t chunk, const gfrs_sjob *jobs,
                              const int64_t *bad, gfrs_sresult *results,
                              int njobs, hipStream_t s);
 
+/* Shard write queue: one bucket of the shard-write schedule (gfrs_plan.h).
+ * An item frames its payload - img = false: raw bytes,
+ *   payload of frame f at src + item.src + f * 65532,
+ * img = true: the body of a disk image,
+ *   payload of frame f at src + item.src + 32 + f * 65536 + 4 -
+ * into the new image at dst + item.img: the payload at
+ *   dst + item.img + 32 + f * 65536 + 4
+ * and the computed CRC as the 4-byte LE word in front of it.  The CRC of the
+ * frame at walk position w also goes to fcrc[w] (fcrc already offset by the
+ * bucket's frame_base); with img = true bad[item.job] is lowered to f when the
+ * source's stored word differs (bad preset to -1, compared unsigned).
+ * frame_prefix holds the nitems+1 exclusive prefix sums of the items' frames,
+ * total_frames its last entry. */
+void launch_shard_write_frame_queue(uint8_t *dst, uint64_t src,
+                                    const gfrs_witem *items,
+                                    const uint64_t *frame_prefix,
+                                    uint32_t nitems, uint64_t total_frames,
+                                    bool img, uint32_t *fcrc, int64_t *bad,
+                                    hipStream_t s);
+/* ... and its headers, footers and results, one wave per job after the frame
+ * buckets: the new header, the fold of the job's fcrc words from
+ * fcrc[job_frame[j]] on into the new footer and the result's crc, and for
+ * SRC_IMAGE jobs the source's header bits and fields, BODY_CRC from bad[j]
+ * and the two footer bits. */
+void launch_shard_write_head_queue(uint8_t *dst, uint64_t src,
+                                   const gfrs_wjob *jobs,
+                                   const uint64_t *job_frame,
+                                   const uint32_t *fcrc, const int64_t *bad,
+                                   gfrs_sresult *results, int njobs,
+                                   hipStream_t s);
+
 /* EncodeIdx-style accumulate apply (reedsolomon.go:631-668):
  * out[r] ^= coeff[r]*in for one input shard. */
 void launch_rs_apply_xor(const uint64_t *ptrs, int nptr,

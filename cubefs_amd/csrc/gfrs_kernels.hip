@@ -5877,6 +5877,374 @@ void launch_shard_head_queue(uint64_t chunk, const gfrs_sjob *jobs,
                      chunk, jobs, job_frame, fcrc, bad, results, njobs);
 }
 
+/* ---- shard write queue: frame payloads into new disk images ---- */
+
+/* The write direction over disk images: a payload in, a new image body out.
+ * The walk is shard_read_frame_queue_k's - a contiguous frame range per
+ * block, one binary search then a forward walk over the prefix sums, scalar
+ * item loads, every pointer rebuilt from the item - over ALL frames of an
+ * item, so frame f of the walk is frame f of both images.  The frame is that
+ * kernel's too: per 16 KiB pass a lane Horner-chains its four 16-byte pieces
+ * through the register CRC (crc16_reg / shift4k) and folds by its position
+ * operator - the same operators, the same partial-frame rule - and the ragged
+ * tail bytes take one lane each; a frame costs one wave reduction.  No GF
+ * tables, no descriptor, no MAC.
+ * IMG = false reads raw bytes (frame f at item.src + f * 65532), IMG = true
+ * the body of a source image (item.src + 32 + f * 65536 + 4); either may sit
+ * at any byte address.  What was loaded is stored at
+ * dst + item.img + 32 + f * 65536 + 4, which is 4-aligned: a 16-byte piece
+ * goes out as one 16-byte store when the frame's payload address is a
+ * multiple of 16 (block-uniform), as four dwords otherwise; the ragged tail
+ * bytes are gathered four lanes to a dword, and only the partial last dword
+ * of a shard is stored by bytes.
+ * Lane 0 stores the computed CRC as the frame's 4-byte LE word, writes it to
+ * fcrc[walk index] and - IMG only - lowers bad[item.job] to f when the
+ * source's stored word differs.
+ * No lane leaves the frame loop early; no load leaves the item's source
+ * bytes; no store leaves the new image's body. */
+template <bool IMG, int WPS>
+__global__ __launch_bounds__(CRC_BLOCKT, WPS) void shard_write_frame_queue_k(
+    uint8_t *__restrict__ dst, uint64_t src,
+    const gfrs_witem *__restrict__ items,
+    const uint64_t *__restrict__ frame_prefix, uint32_t nitems,
+    uint64_t total_frames, uint32_t *__restrict__ fcrc,
+    unsigned long long *__restrict__ bad) {
+  constexpr int EF_PASS = 16384;
+  constexpr int EF_PASSES = 4;
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+  constexpr uint32_t INV16K = 0x479933FCu;
+
+  const uint64_t per_blk = (total_frames + gridDim.x - 1) / gridDim.x;
+  const uint64_t f_lo = uint64_t(blockIdx.x) * per_blk;
+  const uint64_t f_hi =
+      f_lo + per_blk < total_frames ? f_lo + per_blk : total_frames;
+  if (f_lo >= f_hi) return; /* whole block, before any barrier */
+
+  __shared__ __attribute__((aligned(16))) uint32_t tab[8][256];
+  __shared__ uint32_t stab[4][256];
+  __shared__ uint32_t red[4];
+  __shared__ uint32_t x8tab[16];
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift4k[0][0])[i];
+  if (threadIdx.x == 0) {
+    uint32_t v = 0x80000000u;
+    for (int j = 0; j < 16; j++) {
+      x8tab[j] = v;
+      v = gf2_mulmod_d(v, g_pow8[0]);
+    }
+  }
+  const int lane16i = int(threadIdx.x) * 16;
+  const uint32_t op_pA =
+      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16i + 16)));
+  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
+  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
+  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  const uint32_t it_full =
+      gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
+  __syncthreads();
+
+  /* largest it with frame_prefix[it] <= f_lo (frame_prefix[0] == 0) */
+  uint32_t it = 0;
+  for (uint32_t hi = nitems; hi - it > 1;) {
+    const uint32_t mid = it + (hi - it) / 2;
+    if (frame_prefix[mid] <= f_lo)
+      it = mid;
+    else
+      hi = mid;
+  }
+
+  for (uint64_t fr = f_lo; fr < f_hi; fr++) {
+    while (frame_prefix[it + 1] <= fr) it++; /* it + 1 <= nitems */
+    const gfrs_witem item = items[it];
+    const int64_t f = int64_t(fr - frame_prefix[it]);
+    const int payload =
+        int(i64min(payload_full, int64_t(item.size) - f * payload_full));
+    /* pb: the frame's payload in the source; db: the frame in the new image,
+     * its CRC word first */
+    const uint8_t *pb =
+        IMG ? as_global(src + item.src + 32) + f * block_len + CRC_LEN
+            : as_global(src + item.src) + f * payload_full;
+    uint8_t *db = reinterpret_cast<uint8_t *>(uint64_t(dst) + item.img + 32) +
+                  f * block_len;
+    uint8_t *dp = db + CRC_LEN;
+    const bool al16 = (uint64_t(dp) & 15) == 0; /* block-uniform */
+
+    uint32_t part = 0;
+#pragma unroll 1
+    for (int h = 0; h < EF_PASSES; h++) {
+      const int r0 = h * EF_PASS;
+      const int rbi = payload - r0 < EF_PASS ? payload - r0 : EF_PASS;
+      if (rbi <= 0) break; /* block-uniform */
+
+      uint4 v[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        v[i] = off + 16 <= rbi
+                   ? *reinterpret_cast<const uint4 *>(pb + r0 + off)
+                   : uint4{0, 0, 0, 0};
+      }
+
+      uint32_t op = h == 0   ? op_pA
+                    : h == 1 ? op_pB
+                    : h == 2 ? op_pC
+                             : op_pD;
+      if (h == EF_PASSES - 1 && threadIdx.x == 255)
+        op = shift4k(op, stab); /* lane 255's last pass has 3 pieces */
+      if (payload != int(payload_full)) {
+        int np = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (i * 4096 + lane16i + 16 <= rbi) np = i + 1;
+        const int end = np ? r0 + (np - 1) * 4096 + lane16i + 16 : r0;
+        op = x8n_d(uint64_t(payload - end));
+      }
+
+      uint32_t t = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        if (off + 16 <= rbi) t = shift4k(t, stab) ^ crc16_reg(v[i], tab);
+      }
+      part ^= t ? gf2_mulmod_d(op, t) : 0;
+
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        if (off + 16 <= rbi) {
+          uint8_t *q = dp + r0 + off;
+          if (al16) {
+            *reinterpret_cast<uint4 *>(q) = v[i];
+          } else {
+            uint32_t *dw = reinterpret_cast<uint32_t *>(q);
+            dw[0] = v[i].x; dw[1] = v[i].y; dw[2] = v[i].z; dw[3] = v[i].w;
+          }
+        }
+      }
+      if (rbi & 15) { /* ragged tail of the frame: one lane per byte */
+        const int nt = rbi & 15;
+        const int tl = int(threadIdx.x);
+        const int p = (rbi & ~15) + tl;
+        uint32_t x = 0;
+        if (tl < nt) {
+          x = pb[r0 + p];
+          part ^= gf2_mulmod_d(x8tab[rbi - 1 - p], tab[0][x]);
+        }
+        /* four lanes' bytes as one LE dword in the lowest of them; lanes
+         * behind the tail hold 0.  The branch is block-uniform, so every
+         * lane takes part in the shuffles */
+        const uint32_t w = x | (__shfl_down(x, 1, 64) << 8) |
+                           (__shfl_down(x, 2, 64) << 16) |
+                           (__shfl_down(x, 3, 64) << 24);
+        if (tl < nt && (tl & 3) == 0) {
+          uint8_t *q = dp + r0 + p; /* r0 + p is a multiple of 4 */
+          if (tl + 4 <= nt) {
+            *reinterpret_cast<uint32_t *>(q) = w;
+          } else { /* the partial last dword of the shard */
+#pragma unroll
+            for (int b = 0; b < 3; b++)
+              if (tl + b < nt) q[b] = uint8_t(w >> (8 * b));
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) part ^= __shfl_xor(part, sh, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t itv =
+          payload == int(payload_full)
+              ? it_full
+              : gf2_mulmod_d(x8n_d(uint64_t(payload)), 0xFFFFFFFFu);
+      const uint32_t crc = ~(itv ^ red[0] ^ red[1] ^ red[2] ^ red[3]);
+      *reinterpret_cast<uint32_t *>(db) = crc; /* the LE frame word */
+      fcrc[fr] = crc;
+      if (IMG) {
+        const uint8_t *sb = pb - CRC_LEN;
+        const uint32_t want = uint32_t(sb[0]) | (uint32_t(sb[1]) << 8) |
+                              (uint32_t(sb[2]) << 16) |
+                              (uint32_t(sb[3]) << 24);
+        if (want != crc)
+          atomicMin(&bad[item.job], static_cast<unsigned long long>(f));
+      }
+    }
+    __syncthreads(); /* red is the next frame's too */
+  }
+}
+
+void launch_shard_write_frame_queue(uint8_t *dst, uint64_t src,
+                                    const gfrs_witem *items,
+                                    const uint64_t *frame_prefix,
+                                    uint32_t nitems, uint64_t total_frames,
+                                    bool img, uint32_t *fcrc, int64_t *bad,
+                                    hipStream_t s) {
+  if (nitems == 0 || total_frames == 0) return;
+  /* the cap of the other frame queues, read on every launch: GFRS_CRC_GRID
+   * forces the multi-frame walk at tiny shapes */
+  const uint64_t cap = uint64_t(env_grid("GFRS_CRC_GRID", 16384));
+  const int grid = int(total_frames < cap ? total_frames : cap);
+  /* waves per SIMD: 8; GFRS_SWR_WAVES = 4 or 8
+   * overrides it and, like GFRS_SRD_WAVES, is read on every launch, so a test
+   * can run both builds */
+  const char *we = getenv("GFRS_SWR_WAVES");
+  const int wv = we ? atoi(we) : 0;
+  unsigned long long *ubad = reinterpret_cast<unsigned long long *>(bad);
+#define GFRS_SWR_GO(IM, W)                                                  \
+  hipLaunchKernelGGL((shard_write_frame_queue_k<IM, W>), dim3(grid),        \
+                     dim3(CRC_BLOCKT), 0, s, dst, src, items, frame_prefix, \
+                     nitems, total_frames, fcrc, ubad)
+  if (img) {
+    if (wv == 4) GFRS_SWR_GO(true, 4);
+    else GFRS_SWR_GO(true, 8);
+  } else {
+    if (wv == 4) GFRS_SWR_GO(false, 4);
+    else GFRS_SWR_GO(false, 8);
+  }
+#undef GFRS_SWR_GO
+}
+
+/* One wave per job, after the frame buckets on the same stream: write the new
+ * 32-byte header (shard_finalize_queue_k's code, from the job), fold the job's
+ * computed frame CRCs into the CRC of the whole payload - the operator of a
+ * full frame once, another only for the last frame, the words loaded 64 to a
+ * wave as in shard_head_queue_k - and write the footer.  For a SRC_IMAGE job
+ * parse the source's header and footer by shard_head_queue_k's rules into the
+ * status bits and the stored fields; a raw job reports its own ids and
+ * status 0.  Geometry follows the job's size, never the source header's. */
+__global__ void shard_write_head_queue_k(uint8_t *__restrict__ dst,
+                                         uint64_t src,
+                                         const gfrs_wjob *__restrict__ jobs,
+                                         const uint64_t *__restrict__ job_frame,
+                                         const uint32_t *__restrict__ fcrc,
+                                         const int64_t *__restrict__ bad,
+                                         gfrs_sresult *__restrict__ results,
+                                         int njobs) {
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+  const int j = blockIdx.x * (blockDim.x / 64) + (threadIdx.x / 64);
+  const int lane = threadIdx.x & 63;
+  if (j >= njobs) return; /* whole wave */
+  /* every lane does the wave-uniform work below; lane 0 does the stores */
+  const gfrs_wjob jb = jobs[j];
+  uint8_t *img = dst + jb.img_off;
+  const int64_t raw_size = int64_t(jb.size);
+  const int64_t nframes = (raw_size + payload_full - 1) / payload_full;
+  { /* the 32 B header (shard.go:241-261), big-endian fields */
+    uint32_t w[8];
+    w[1] = 0xccefcdabu; /* ab cd ef cc */
+    w[2] = __builtin_bswap32(uint32_t(jb.bid >> 32));
+    w[3] = __builtin_bswap32(uint32_t(jb.bid));
+    w[4] = __builtin_bswap32(uint32_t(jb.vuid >> 32));
+    w[5] = __builtin_bswap32(uint32_t(jb.vuid));
+    w[6] = __builtin_bswap32(uint32_t(raw_size));
+    w[7] = 0;
+    uint32_t c = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 1; i < 8; i++) {
+      const uint32_t x = w[i];
+#pragma unroll
+      for (int b = 0; b < 4; b++)
+        c = g_crc_tab4[0][(c ^ (x >> (8 * b))) & 0xFF] ^ (c >> 8);
+    }
+    w[0] = __builtin_bswap32(~c);
+    uint32_t *d32 = reinterpret_cast<uint32_t *>(img);
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < 8; i++) d32[i] = w[i];
+    }
+  }
+  uint32_t crc = 0;
+  {
+    const uint32_t *fc = fcrc + job_frame[j];
+    const uint32_t op_full = x8n_d(uint64_t(payload_full));
+    int64_t remain = raw_size;
+    /* the fold is serial, its loads are not: 64 words per wave load */
+    for (int64_t f0 = 0; f0 < nframes; f0 += 64) {
+      const uint32_t mine = f0 + lane < nframes ? fc[f0 + lane] : 0;
+      const int nf = int(nframes - f0 < 64 ? nframes - f0 : 64);
+      for (int i = 0; i < nf; i++) {
+        const uint32_t fcv = __shfl(mine, i, 64);
+        const int64_t plen = remain < payload_full ? remain : payload_full;
+        if (f0 + i == 0) {
+          crc = fcv;
+        } else {
+          const uint32_t op =
+              plen == payload_full ? op_full : x8n_d(uint64_t(plen));
+          crc = gf2_mulmod_d(op, crc) ^ fcv;
+        }
+        remain -= plen;
+      }
+    }
+  }
+  const int64_t ftr_off = 32 + (raw_size + CRC_LEN * nframes);
+  if (lane == 0) {
+    uint8_t *ftr = img + ftr_off;
+    ftr[0] = 0xcc; ftr[1] = 0xef; ftr[2] = 0xcd; ftr[3] = 0xab;
+    ftr[4] = uint8_t(crc >> 24); ftr[5] = uint8_t(crc >> 16); /* BE */
+    ftr[6] = uint8_t(crc >> 8); ftr[7] = uint8_t(crc);
+  }
+  gfrs_sresult r;
+  r.status = 0;
+  r.crc = crc;
+  r.bad_block = -1;
+  r.bid = jb.bid;
+  r.vuid = jb.vuid;
+  r.size = jb.size;
+  if (jb.flags & GFRS_WJOB_SRC_IMAGE) { /* wave-uniform */
+    const uint8_t *si = as_global(src + jb.src_off);
+    uint32_t status = 0;
+    if (!(si[4] == 0xab && si[5] == 0xcd && si[6] == 0xef && si[7] == 0xcc))
+      status |= GFRS_SHARD_HDR_MAGIC;
+    uint32_t hcrc = 0xFFFFFFFFu;
+    for (int i = 4; i < 32; i++)
+      hcrc = g_crc_tab4[0][(hcrc ^ si[i]) & 0xFF] ^ (hcrc >> 8);
+    hcrc = ~hcrc;
+    const uint32_t want_h = (uint32_t(si[0]) << 24) | (uint32_t(si[1]) << 16) |
+                            (uint32_t(si[2]) << 8) | uint32_t(si[3]);
+    if (want_h != hcrc) status |= GFRS_SHARD_HDR_CRC;
+    uint64_t bid = 0, vuid = 0;
+    for (int i = 0; i < 8; i++) bid = (bid << 8) | si[8 + i];
+    for (int i = 0; i < 8; i++) vuid = (vuid << 8) | si[16 + i];
+    const uint64_t size = (uint64_t(si[24]) << 24) | (uint64_t(si[25]) << 16) |
+                          (uint64_t(si[26]) << 8) | uint64_t(si[27]);
+    if (bid != jb.src_bid || vuid != jb.src_vuid || size != jb.size)
+      status |= GFRS_SHARD_HDR_MISMATCH;
+    const int64_t bb = bad[j];
+    if (bb != -1) status |= GFRS_SHARD_BODY_CRC;
+    const uint8_t *ftr = si + ftr_off;
+    if (!(ftr[0] == 0xcc && ftr[1] == 0xef && ftr[2] == 0xcd &&
+          ftr[3] == 0xab))
+      status |= GFRS_SHARD_FTR_MAGIC;
+    const uint32_t want_f = (uint32_t(ftr[4]) << 24) |
+                            (uint32_t(ftr[5]) << 16) |
+                            (uint32_t(ftr[6]) << 8) | uint32_t(ftr[7]);
+    if (want_f != crc) status |= GFRS_SHARD_FTR_CRC;
+    r.status = status;
+    r.bad_block = bb;
+    r.bid = bid;
+    r.vuid = vuid;
+    r.size = size;
+  }
+  if (lane == 0) results[j] = r;
+}
+
+void launch_shard_write_head_queue(uint8_t *dst, uint64_t src,
+                                   const gfrs_wjob *jobs,
+                                   const uint64_t *job_frame,
+                                   const uint32_t *fcrc, const int64_t *bad,
+                                   gfrs_sresult *results, int njobs,
+                                   hipStream_t s) {
+  if (njobs <= 0) return;
+  const int wps = 4; /* waves per block */
+  const int blocks = (njobs + wps - 1) / wps;
+  hipLaunchKernelGGL(shard_write_head_queue_k, dim3(blocks), dim3(wps * 64), 0,
+                     s, dst, src, jobs, job_frame, fcrc, bad, results, njobs);
+}
+
 /* Host-side one-time init of the device CRC tables (g_crc_tab4, g_pow8)
  * for the CURRENT device.  Called by gfrs_host.cpp under its device mutex. */
 int crc_device_init_current(void) {

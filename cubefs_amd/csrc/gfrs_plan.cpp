@@ -809,9 +809,83 @@ int shard_read_schedule(const gfrs_sjob *jobs, int njobs, uint64_t out_addr,
   return GFRS_OK;
 }
 
+/* ---- the shard write queue ---- */
+
+int shard_write_schedule(const gfrs_wjob *jobs, int njobs, uint64_t dst_addr,
+                         ShardWriteSchedule *out) {
+  *out = ShardWriteSchedule();
+  if (njobs <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
+  constexpr uint32_t known = GFRS_WJOB_SRC_IMAGE;
+  size_t count[2] = {0, 0};
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_wjob &jb = jobs[j];
+    if (jb.reserved != 0 || (jb.flags & ~known)) return GFRS_ERR_INVALID_SHARDS;
+    if (jb.size == 0) return GFRS_ERR_SHARD_NO_DATA;
+    if (jb.size >> 32) return GFRS_ERR_INVALID_SHARDS;
+    if ((dst_addr + jb.img_off) % 4) return GFRS_ERR_INVALID_SHARDS;
+    count[(jb.flags & GFRS_WJOB_SRC_IMAGE) ? 1 : 0]++;
+  }
+  size_t fill[2] = {0, 0}, pre[2] = {0, 0};
+  for (int b = 0, nitems = 0; b < 2; b++) {
+    if (!count[b]) continue;
+    ShardWriteBucket bk;
+    bk.src_image = b;
+    bk.first = fill[b] = size_t(nitems);
+    bk.count = count[b];
+    bk.prefix = pre[b] = size_t(nitems) + out->buckets.size();
+    nitems += int(count[b]);
+    out->buckets.push_back(bk);
+  }
+  out->items.resize(size_t(njobs));
+  out->frame_prefix.assign(size_t(njobs) + out->buckets.size(), 0);
+  out->job_frame.assign(size_t(njobs), 0);
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_wjob &jb = jobs[j];
+    const int b = (jb.flags & GFRS_WJOB_SRC_IMAGE) ? 1 : 0;
+    out->items[fill[b]++] =
+        gfrs_witem{jb.src_off, jb.size, jb.img_off, j, jb.flags};
+    const size_t pi = pre[b]++;
+    out->job_frame[j] = out->frame_prefix[pi]; /* + frame_base, below */
+    out->frame_prefix[pi + 1] =
+        out->frame_prefix[pi] + (jb.size + REPAIR_PAYLOAD - 1) / REPAIR_PAYLOAD;
+  }
+  for (ShardWriteBucket &bk : out->buckets) {
+    bk.frame_base = out->total_frames;
+    out->total_frames += out->frame_prefix[bk.prefix + bk.count];
+  }
+  if (out->buckets.size() == 2)
+    for (int j = 0; j < njobs; j++)
+      if (jobs[j].flags & GFRS_WJOB_SRC_IMAGE)
+        out->job_frame[j] += out->buckets[1].frame_base;
+  return GFRS_OK;
+}
+
 }  // namespace gfrs
 
 /* ---- GPU-free diagnostic export (include/gfrs.h) ---- */
+
+extern "C" int gfrs_compute_shard_write_queue_schedule(
+    const gfrs_wjob *jobs, int njobs, int64_t block_len, int item_cap,
+    gfrs_witem *items, uint64_t *frame_prefix, int *nitems,
+    gfrs_wbucket *buckets, int *nbuckets, uint64_t *total_frames) {
+  using namespace gfrs;
+  int rc = encode_queue_block_check(block_len);
+  if (rc != GFRS_OK) return rc;
+  ShardWriteSchedule s;
+  if ((rc = shard_write_schedule(jobs, njobs, 0, &s)) != GFRS_OK) return rc;
+  if (s.items.size() > size_t(item_cap < 0 ? 0 : item_cap))
+    return GFRS_ERR_NOMEM;
+  *nitems = int(s.items.size());
+  *nbuckets = int(s.buckets.size());
+  *total_frames = s.total_frames;
+  std::copy(s.items.begin(), s.items.end(), items);
+  std::copy(s.frame_prefix.begin(), s.frame_prefix.end(), frame_prefix);
+  for (size_t b = 0; b < s.buckets.size(); b++)
+    buckets[b] =
+        gfrs_wbucket{s.buckets[b].src_image, int32_t(s.buckets[b].first),
+                     int32_t(s.buckets[b].count), 0};
+  return GFRS_OK;
+}
 
 extern "C" int gfrs_compute_shard_read_queue_schedule(
     const gfrs_sjob *jobs, int njobs, int64_t block_len, int item_cap,

@@ -382,6 +382,38 @@ inline uint64_t shard_last_frame(const gfrs_sjob &j) {
 int shard_read_schedule(const gfrs_sjob *jobs, int njobs, uint64_t out_addr,
                         bool have_out, ShardReadSchedule *out);
 
+/* ---- the shard write queue (gfrs_shard_write_queue) ----
+ * Frame payloads - raw bytes, or the body of an existing disk image - into
+ * new disk images.  Again no coding plan: the schedule splits the jobs into
+ * the two builds of the frame kernel, raw jobs first, then SRC_IMAGE jobs,
+ * each bucket in caller order with the count+1 exclusive prefix sums of its
+ * items' frames.  The computed CRC of the frame at walk position w of bucket
+ * b is kept at frame_base(b) + w of the context's scratch, job_frame[j] being
+ * the place of job j's first frame there (the head kernel folds every job's
+ * words from it). */
+struct ShardWriteBucket {
+  int src_image = 0;
+  size_t first = 0, count = 0; /* items[first, first+count) */
+  size_t prefix = 0; /* its count+1 frame prefix sums start here
+                        (= first + bucket index) */
+  uint64_t frame_base = 0; /* frames of the bucket before it */
+};
+
+struct ShardWriteSchedule {
+  std::vector<gfrs_witem> items;      /* both buckets' items, back to back */
+  std::vector<uint64_t> frame_prefix; /* exclusive prefix sums of the items'
+                                         frames, ceil(size / 65532) */
+  std::vector<ShardWriteBucket> buckets; /* raw, then SRC_IMAGE */
+  std::vector<uint64_t> job_frame;    /* njobs entries, caller order */
+  uint64_t total_frames = 0;
+};
+
+/* Job validation (gfrs.h, shard-write-queue contract; dst_addr = the address
+ * of dst, for the alignment rule) and the schedule.  block_len goes through
+ * encode_queue_block_check. */
+int shard_write_schedule(const gfrs_wjob *jobs, int njobs, uint64_t dst_addr,
+                         ShardWriteSchedule *out);
+
 }  // namespace gfrs
 
 #endif

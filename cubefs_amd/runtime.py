@@ -256,6 +256,45 @@ class SBucket(ctypes.Structure):
     ]
 
 
+WJOB_SRC_IMAGE = 1
+
+
+class WJob(ctypes.Structure):
+    """gfrs_wjob: one job of a shard write queue."""
+    _fields_ = [
+        ("src_off", ctypes.c_uint64),
+        ("size", ctypes.c_uint64),
+        ("bid", ctypes.c_uint64),
+        ("vuid", ctypes.c_uint64),
+        ("src_bid", ctypes.c_uint64),
+        ("src_vuid", ctypes.c_uint64),
+        ("img_off", ctypes.c_uint64),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class WItem(ctypes.Structure):
+    """gfrs_witem: one work item of a shard-write schedule."""
+    _fields_ = [
+        ("src", ctypes.c_uint64),
+        ("size", ctypes.c_uint64),
+        ("img", ctypes.c_uint64),
+        ("job", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+    ]
+
+
+class WBucket(ctypes.Structure):
+    """gfrs_wbucket: one frame launch of a shard-write schedule."""
+    _fields_ = [
+        ("src_image", ctypes.c_int32),
+        ("first", ctypes.c_int32),
+        ("count", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -394,6 +433,13 @@ def lib():
         L.gfrs_compute_shard_read_queue_schedule.argtypes = [
             ctypes.POINTER(SJob), ctypes.c_int, i64, ctypes.c_int,
             ctypes.POINTER(SItem), u64p, ip, ctypes.POINTER(SBucket), ip,
+            u64p]
+        L.gfrs_shard_write_queue.argtypes = [vp, vp, vp, ctypes.POINTER(WJob),
+                                             ctypes.c_int, i64,
+                                             ctypes.POINTER(SResult)]
+        L.gfrs_compute_shard_write_queue_schedule.argtypes = [
+            ctypes.POINTER(WJob), ctypes.c_int, i64, ctypes.c_int,
+            ctypes.POINTER(WItem), u64p, ip, ctypes.POINTER(WBucket), ip,
             u64p]
         _lib = L
     return _lib

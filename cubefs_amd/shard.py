@@ -9,8 +9,8 @@ header CRCs — the payload crosses HBM exactly once.
 """
 import ctypes
 
-from .runtime import (GfrsError, SJob, SResult, Tactic, check,  # noqa: F401
-                      lib, SJOB_FOOTER, SJOB_NO_OUT)
+from .runtime import (GfrsError, SJob, SResult, Tactic, WJob,  # noqa: F401
+                      check, lib, SJOB_FOOTER, SJOB_NO_OUT, WJOB_SRC_IMAGE)
 
 HEADER_SIZE = 32
 FOOTER_SIZE = 8
@@ -82,6 +82,26 @@ class ShardCodec:
         check(lib().gfrs_shard_read_queue(
             self._ctx, None if out is None else out.data_ptr(),
             chunk.data_ptr(), arr, nj, block_len, res), "shard_read_queue")
+        return [{"status": r.status, "crc": r.crc, "bad_block": r.bad_block,
+                 "bid": r.bid, "vuid": r.vuid, "size": r.size}
+                for r in res[:nj]]
+
+    def write_queue(self, dst, src, jobs, block_len=DEFAULT_BLOCK):
+        """Write many disk images of different sizes in one call
+        (gfrs_shard_write_queue), from raw bytes or - WJOB_SRC_IMAGE - from
+        the payload of an existing image, which is checked on the way
+        (compaction).  dst, src: flat uint8 device tensors; jobs: [(src_off,
+        size, bid, vuid, src_bid, src_vuid, img_off, flags)].  Returns a list
+        of dicts {status, crc, bad_block, bid, vuid, size}, one per job in the
+        caller's order; crc is the CRC32 of the payload written."""
+        nj = len(jobs)
+        arr = (WJob * max(1, nj))()
+        for j, job in enumerate(jobs):
+            arr[j] = WJob(*job, 0)
+        res = (SResult * max(1, nj))()
+        check(lib().gfrs_shard_write_queue(
+            self._ctx, dst.data_ptr(), src.data_ptr(), arr, nj, block_len,
+            res), "shard_write_queue")
         return [{"status": r.status, "crc": r.crc, "bad_block": r.bad_block,
                  "bid": r.bid, "vuid": r.vuid, "size": r.size}
                 for r in res[:nj]]

@@ -752,6 +752,81 @@ int gfrs_shard_read_queue(gfrs_ctx *ctx, void *out, const void *chunk,
                           const gfrs_sjob *jobs, int njobs, int64_t block_len,
                           gfrs_sresult *results /* njobs, host */);
 
+/* ---- shard write queue (datafile.go:342-384 Write: the loop over the bids
+ * of a batch of PUTs; compact.go:236-344 doCompact: the loop over the bids of
+ * the chunk being compacted) ----
+ * gfrs_shard_write_batch as a queue over shards of different sizes: every job
+ * names a payload - raw bytes, or with GFRS_WJOB_SRC_IMAGE the payload of an
+ * existing disk image - the ids of the new header and the place of the new
+ * image.  The payload is read once, its frame CRCs are computed from the bytes
+ * that were read, and the new image is written; a SRC_IMAGE job also gets the
+ * answer gfrs_shard_read_queue would give about its source.  Every job gets
+ * back the CRC32-IEEE of its payload, the shard meta's Crc.  jobs and results
+ * are host memory, src and dst device pointers.
+ *
+ * Shard-write-queue contract (pinned by tests/test_gpu_shard_write_queue.py):
+ *  - Per-job image.  The gfrs_shard_disk_size(size, 65536) bytes at
+ *    dst + img_off are byte-identical to the reference's shard write of the
+ *    job's payload with the job's bid and vuid: header, freshly computed frame
+ *    CRCs, payload, footer.  The payload of a raw job is
+ *    src[src_off, src_off + size); that of a SRC_IMAGE job the payload bytes
+ *    of the source image as stored, whatever the job's status - geometry
+ *    follows the job's size, never the source header's; what was loaded is
+ *    what is stored.  The new image is always self-consistent; on
+ *    status != 0 the caller drops it, as the reference fails the compaction of
+ *    that bid.  A raw job alone writes the bytes of gfrs_shard_write_batch
+ *    with nshards = 1.
+ *  - Per-job result.  crc is the CRC32-IEEE of the size payload bytes written
+ *    (shard.Crc of datafile.go:379, the footer's value).  A raw job reports
+ *    status = 0, bad_block = -1 and bid, vuid, size as its own.  A SRC_IMAGE
+ *    job reports exactly what a gfrs_shard_read_queue job with from = 0,
+ *    to = size, GFRS_SJOB_FOOTER, bid = src_bid and vuid = src_vuid reports on
+ *    the source image: the six independent status bits, bad_block, crc and the
+ *    header fields as stored.
+ *  - Layout.  Sources need no alignment; src is never written.  dst + img_off
+ *    is a multiple of 4.  In dst only the declared images are written: nothing
+ *    between them, nothing past an image's disk size.  Only the job's source
+ *    bytes are read: for SRC_IMAGE the 32-byte header, every frame whole and
+ *    the 8-byte footer; for a raw job its size bytes.  Overlapping images, or
+ *    src overlapping dst, are caller errors (not checked).
+ *  - Validation.  Everything is validated before the first launch, and any
+ *    error returns its code and writes nothing, neither in dst nor in
+ *    results:
+ *      GFRS_ERR_INVALID_BLOCK for block_len <= 0 or not a multiple of 4096;
+ *      GFRS_ERR_UNSUPPORTED for any other block_len != 65536;
+ *      GFRS_ERR_SHARD_NO_DATA for size == 0;
+ *      GFRS_ERR_INVALID_SHARDS for njobs <= 0, size >= 2^32, reserved != 0,
+ *      unknown flag bits, or a misaligned dst + img_off.
+ *  - Blocking.  The call blocks until the results are ready; it runs on the
+ *    context stream, takes the context mutex once and makes one upload of one
+ *    blob, one read-back and one sync.  It obeys the ordering contract above:
+ *    its upload waits out an id upload that an async gfrs_shard_write_batch
+ *    left queued.
+ *  - Launch bound.  At most 3 kernel launches whatever njobs is: the raw
+ *    jobs, the SRC_IMAGE jobs, and one launch of one wave per job that writes
+ *    the new header and footer, checks the source header and footer of a
+ *    SRC_IMAGE job and writes the results.
+ *  - A job of at most 4096 bytes still occupies one workgroup (small jobs are
+ *    not packed together); the footer CRC is folded serially over the job's
+ *    frames. */
+enum { GFRS_WJOB_SRC_IMAGE = 1 };
+
+typedef struct gfrs_wjob {
+  uint64_t src_off;   /* raw shard (size bytes) at src + src_off; with
+                         SRC_IMAGE a disk image there; no alignment */
+  uint64_t size;      /* raw shard size, 1 .. 2^32-1 */
+  uint64_t bid, vuid; /* written into the new header */
+  uint64_t src_bid, src_vuid; /* SRC_IMAGE: what the source header must hold
+                                 (with size); ignored otherwise */
+  uint64_t img_off;   /* new image at dst + img_off; multiple of 4 */
+  uint32_t flags;     /* GFRS_WJOB_* */
+  uint32_t reserved;  /* must be 0 */
+} gfrs_wjob;
+
+int gfrs_shard_write_queue(gfrs_ctx *ctx, void *dst, const void *src,
+                           const gfrs_wjob *jobs, int njobs, int64_t block_len,
+                           gfrs_sresult *results /* njobs, host */);
+
 /* ---- ec.Buffer size math (buf.go:67-133) ---- */
 int gfrs_buffer_sizes(const gfrs_tactic *t, int64_t data_size,
                       int64_t *shard_size, int64_t *ec_data_size,
@@ -962,6 +1037,33 @@ int gfrs_compute_shard_read_queue_schedule(
     const gfrs_sjob *jobs, int njobs, int64_t block_len, int item_cap,
     gfrs_sitem *items, uint64_t *frame_prefix, int *nitems,
     gfrs_sbucket *buckets, int *nbuckets, uint64_t *total_frames);
+/* GPU-free: what gfrs_shard_write_queue would upload for a queue, with the
+ * same builder, so CPU tests can check it without a device.
+ *   Work items: one per job.  At most two buckets, in the fixed order raw
+ *   jobs (src_image = 0), then SRC_IMAGE jobs (src_image = 1); bucket b owns
+ *   items[first, first+count), in caller order, and the count+1 exclusive
+ *   prefix sums of the frames of its items - ceil(size / 65532) - at
+ *   frame_prefix[first + b ...].
+ *   *total_frames is the sum over both buckets: the number of computed frame
+ *   CRCs the engine keeps in scratch (the raw bucket's first, then the
+ *   SRC_IMAGE bucket's, each in walk order).
+ * items holds item_cap entries, frame_prefix item_cap + 2, buckets 2
+ * (GFRS_ERR_NOMEM when the schedule is larger).  Returns the validation codes
+ * of gfrs_shard_write_queue, taking dst as 4-aligned. */
+typedef struct gfrs_witem {
+  uint64_t src;      /* byte offset in src of the raw shard or source image */
+  uint64_t size;     /* raw shard size */
+  uint64_t img;      /* byte offset in dst of the new image */
+  int32_t job;       /* caller's index */
+  uint32_t flags;    /* of the job */
+} gfrs_witem;
+typedef struct gfrs_wbucket {
+  int32_t src_image, first, count, reserved;
+} gfrs_wbucket;
+int gfrs_compute_shard_write_queue_schedule(
+    const gfrs_wjob *jobs, int njobs, int64_t block_len, int item_cap,
+    gfrs_witem *items, uint64_t *frame_prefix, int *nitems,
+    gfrs_wbucket *buckets, int *nbuckets, uint64_t *total_frames);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);

@@ -59,6 +59,18 @@ medians of queue and yardstick each:
      quarter reading the whole shard, a quarter a range of 64 KiB or less: the
      queue vs one gfrs_shard_parse_batch per distinct size, a sync each.
 
+and gfrs_shard_write_queue (--only xyz), in the same form:
+
+ (x) raw      512 raw shards x 4 MiB into 512 images: the queue vs ONE
+     gfrs_shard_write_batch of the same shards (plus its sync).
+ (y) compact  the same 512 images as SRC_IMAGE jobs into a new chunk: the
+     queue vs the composition it replaces, gfrs_shard_read_queue (whole shard,
+     storing, FOOTER) into a raw scratch buffer, then gfrs_shard_write_batch.
+ (z) mixed    the 4096-job size mix of (b), half raw and half SRC_IMAGE: the
+     queue vs one composition per distinct size (a write batch of the raw
+     shards of that size; a read queue and a write batch of its images), a
+     sync each.
+
 (a) and (d) run on random data with encoded parity; the others on a zeroed buffer
 (a valid stripe: zero parity), since the kernels' work does not depend on
 the data.  One JSON line on stdout; --out also writes it to a file.
@@ -758,6 +770,175 @@ def shard_main(a, out):
         torch.cuda.empty_cache()
 
 
+class ShardWriteProbe(ShardProbe):
+    """gfrs_shard_write_queue against the parent's entry points.  Raw shards
+    are zero bytes, source images those of ShardProbe.chunk (ids 5 and 9); the
+    new images of one size lie back to back at the tight 4-aligned stride, so
+    that the same destination serves one gfrs_shard_write_batch per size."""
+
+    def wjobs(self, specs):
+        """specs: (src_off, size, img_off, flags)."""
+        wj = (runtime.WJob * len(specs))()
+        for j, (src, ln, img, flags) in enumerate(specs):
+            wj[j] = runtime.WJob(src, ln, 21 + j, 22, 5, 9, img, flags, 0)
+        return wj, (runtime.SResult * len(specs))()
+
+    def wqueue(self, dst, src, wj, res, check=False):
+        rc = self.L.gfrs_shard_write_queue(self.enc._ctx, dst.data_ptr(),
+                                           src.data_ptr(), wj, len(wj), 65536,
+                                           res)
+        assert rc == 0, rc
+        if check:       # once, outside the timed calls
+            assert not any(r.status for r in res), "status"
+            assert all(r.bad_block == -1 and r.size == j.size
+                       for r, j in zip(res, wj)), "results"
+            assert len({r.crc for r, j in zip(res, wj)
+                        if j.size == wj[0].size}) == 1, "crc"
+
+    def write_batch(self, dst_ptr, stride, src_ptr, ln, count, ids):
+        rc = self.L.gfrs_shard_write_batch(self.enc._ctx, dst_ptr, stride,
+                                           src_ptr, ln, ln, 65536, ids[0],
+                                           ids[1], count)
+        assert rc == 0, rc
+
+    @staticmethod
+    def ids(n):
+        return ((ctypes.c_uint64 * n)(*range(21, 21 + n)),
+                (ctypes.c_uint64 * n)(*([22] * n)))
+
+    def three(self, res, yard, queue, reps):
+        res = ShardProbe.three(res, yard, queue, reps)
+        if "GFRS_SWR_WAVES" in os.environ:
+            res["GFRS_SWR_WAVES"] = os.environ["GFRS_SWR_WAVES"]
+        return res
+
+    def raw(self, njobs, slen, reps):
+        """(x): raw shards vs ONE gfrs_shard_write_batch of the same shards."""
+        stride = (self.L.gfrs_shard_disk_size(slen, 65536) + 3) // 4 * 4
+        src = torch.zeros(njobs * slen, dtype=torch.uint8, device="cuda")
+        dst = torch.empty(njobs * stride, dtype=torch.uint8, device="cuda")
+        wj, wres = self.wjobs([(j * slen, slen, j * stride, 0)
+                               for j in range(njobs)])
+        ids = self.ids(njobs)
+
+        def yardstick():
+            self.write_batch(dst.data_ptr(), stride, src.data_ptr(), slen,
+                             njobs, ids)
+            self.enc.synchronize()
+
+        res = {"njobs": njobs, "shard_len": slen,
+               "moved_GB": round(njobs * (slen + stride) / 1e9, 3)}
+        return self.three(res, yardstick,
+                          lambda check=False: self.wqueue(dst, src, wj, wres,
+                                                          check), reps)
+
+    def compact(self, njobs, slen, reps):
+        """(y): the images as SRC_IMAGE jobs vs gfrs_shard_read_queue (whole
+        shard, storing, FOOTER) into a raw scratch buffer, then
+        gfrs_shard_write_batch."""
+        chunk, groups, offs = self.chunk([slen] * njobs)
+        stride = groups[slen][1]
+        dst = torch.empty(njobs * stride, dtype=torch.uint8, device="cuda")
+        scratch = torch.empty(njobs * slen, dtype=torch.uint8, device="cuda")
+        wj, wres = self.wjobs([(off, slen, j * stride, 1)
+                               for j, off in enumerate(offs)])
+        sj, sres = self.sjobs([(off, slen, 0, slen, j * slen, 2)
+                               for j, off in enumerate(offs)])
+        ids = self.ids(njobs)
+
+        def yardstick():
+            self.queue(scratch.data_ptr(), chunk, sj, sres)
+            self.write_batch(dst.data_ptr(), stride, scratch.data_ptr(), slen,
+                             njobs, ids)
+            self.enc.synchronize()
+
+        res = {"njobs": njobs, "shard_len": slen,
+               "moved_GB": round(njobs * stride * 2 / 1e9, 3)}
+        return self.three(res, yardstick,
+                          lambda check=False: self.wqueue(dst, chunk, wj, wres,
+                                                          check), reps)
+
+    def mixed(self, lens, reps):
+        """(z): half raw, half SRC_IMAGE, vs one composition per distinct
+        size, each with its sync."""
+        rng = random.Random(17)
+        kinds = [rng.randrange(2) for _ in lens]
+        img_lens = [ln for ln, k in zip(lens, kinds) if k]
+        chunk, groups, offs = self.chunk(img_lens)
+        # one source buffer: the images, then the raw shards per size
+        raw_at, at = {}, chunk.numel()
+        for ln in sorted(set(lens)):
+            raw_at[ln] = at
+            at += ln * sum(1 for x, k in zip(lens, kinds) if x == ln and not k)
+        src = torch.zeros(at, dtype=torch.uint8, device="cuda")
+        src[:chunk.numel()].copy_(chunk)
+        del chunk
+        # destination: per size, the raw jobs' images then the image jobs'
+        dplace, at = {}, 0
+        for ln in sorted(set(lens)):
+            stride = (self.L.gfrs_shard_disk_size(ln, 65536) + 3) // 4 * 4
+            nraw = sum(1 for x, k in zip(lens, kinds) if x == ln and not k)
+            nimg = sum(1 for x, k in zip(lens, kinds) if x == ln and k)
+            dplace[ln] = (at, stride, nraw, nimg)
+            at += stride * (nraw + nimg)
+        dst = torch.empty(at, dtype=torch.uint8, device="cuda")
+        nscr = max(ln * d[3] for ln, d in dplace.items())
+        scratch = torch.empty(max(4, nscr), dtype=torch.uint8, device="cuda")
+        seen = {ln: [0, 0] for ln in dplace}
+        specs, ioffs = [], iter(offs)
+        for ln, k in zip(lens, kinds):
+            first, stride, nraw, _ = dplace[ln]
+            i = seen[ln][k]
+            seen[ln][k] += 1
+            if k:
+                specs.append((next(ioffs), ln, first + stride * (nraw + i), 1))
+            else:
+                specs.append((raw_at[ln] + ln * i, ln, first + stride * i, 0))
+        wj, wres = self.wjobs(specs)
+        per = {}
+        for ln, (first, stride, nraw, nimg) in dplace.items():
+            g = groups.get(ln)
+            sj = self.sjobs([(g[0] + g[1] * i, ln, 0, ln, i * ln, 2)
+                             for i in range(nimg)]) if nimg else None
+            per[ln] = (sj, self.ids(max(1, nraw)), self.ids(max(1, nimg)))
+
+        def per_size():
+            for ln, (first, stride, nraw, nimg) in dplace.items():
+                sj, rid, iid = per[ln]
+                if nraw:
+                    self.write_batch(dst.data_ptr() + first, stride,
+                                     src.data_ptr() + raw_at[ln], ln, nraw,
+                                     rid)
+                if nimg:
+                    self.queue(scratch.data_ptr(), src, sj[0], sj[1])
+                    self.write_batch(dst.data_ptr() + first + stride * nraw,
+                                     stride, scratch.data_ptr(), ln, nimg, iid)
+                self.enc.synchronize()
+
+        res = {"njobs": len(lens), "src_bytes": src.numel(),
+               "dst_bytes": dst.numel(), "sizes": len(dplace),
+               "image_jobs": sum(kinds)}
+        return self.three(res, per_size,
+                          lambda check=False: self.wqueue(dst, src, wj, wres,
+                                                          check), reps)
+
+
+def shard_write_main(a, out):
+    p = ShardWriteProbe()
+    if "x" in a.only:
+        out["x_shard_write_raw"] = p.raw(512 // a.scale, 4 * MIB, reps=7)
+        torch.cuda.empty_cache()
+    if "y" in a.only:
+        out["y_shard_compact"] = p.compact(512 // a.scale, 4 * MIB, reps=7)
+        torch.cuda.empty_cache()
+    if "z" in a.only:
+        rng = random.Random(7)               # the lengths of (b)
+        lens = [rng.choice([64 * KIB, MIB, 4 * MIB])
+                for _ in range(4096 // a.scale)]
+        out["z_shard_write_mixed"] = p.mixed(lens, reps=7)
+        torch.cuda.empty_cache()
+
+
 def read_main(a, out):
     p = ReadProbe()
     out["read_tactic"] = "EC12P4"
@@ -805,7 +986,8 @@ def main():
     ap.add_argument("--only", default="abcde",
                     help="which configurations to run, e.g. 'ac'; the "
                     "encode+frame queue's are 'fpghi' (p = f'), the read "
-                    "queue's 'rs', the shard read queue's 'uvw'")
+                    "queue's 'rs', the shard read queue's 'uvw', the shard "
+                    "write queue's 'xyz'")
     a = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "scale": a.scale}
     if set(a.only) & set("fpghi"):
@@ -814,6 +996,8 @@ def main():
         read_main(a, out)
     if set(a.only) & set("uvw"):
         shard_main(a, out)
+    if set(a.only) & set("xyz"):
+        shard_write_main(a, out)
     if not set(a.only) & set("abcde"):
         line = json.dumps(out)
         print(line)
