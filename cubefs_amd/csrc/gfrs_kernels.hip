@@ -826,6 +826,25 @@ GFRS_DEV uint32_t crc16_reg(const uint4 q, const uint32_t (*tab)[256]) {
   return c;
 }
 
+/* u(q) = q(x) mod P of 16 bytes held in a register uint4: crc16_reg
+ * without its last x^32, so crc16_reg(q) = u(q) * x^32.  The first two
+ * dwords reduce over tab[7..0] (8 independent gathers), the third joins
+ * and reduces over tab[3..0] (4 gathers), the fourth enters as it stands.
+ * A caller that Horner-chains u values and multiplies the chain by x^(8n)
+ * uses x^(8(n+4)) instead: 12 gathers per piece, not 16. */
+GFRS_DEV uint32_t crc12u_reg(const uint4 q, const uint32_t (*tab)[256]) {
+  const uint32_t c =
+      xor3(xor3(tab[7][q.x & 0xFF], tab[6][(q.x >> 8) & 0xFF],
+                tab[5][(q.x >> 16) & 0xFF]),
+           xor3(tab[4][q.x >> 24], tab[3][q.y & 0xFF],
+                tab[2][(q.y >> 8) & 0xFF]),
+           tab[1][(q.y >> 16) & 0xFF] ^ tab[0][q.y >> 24]);
+  const uint32_t w = c ^ q.z;
+  return xor3(xor3(tab[3][w & 0xFF], tab[2][(w >> 8) & 0xFF],
+                   tab[1][(w >> 16) & 0xFF]),
+              tab[0][w >> 24], q.w);
+}
+
 GFRS_DEV uint32_t shift4k(uint32_t c, const uint32_t (*stab)[256]) {
   return xor3(stab[0][c & 0xFF], stab[1][(c >> 8) & 0xFF],
               stab[2][(c >> 16) & 0xFF]) ^
@@ -1889,8 +1908,10 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_reg_k(
    * the chained value times x^(8*4096), i.e. one shift4k.  One register
    * instead of an op_full[4] array. */
   constexpr uint32_t INV16K = 0x479933FCu;
+  /* the chain is built from crc12u_reg pieces, each short of the raw CRC
+   * by x^32: every operator that multiplies it carries 4 bytes more */
   const uint32_t op_first =
-      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16 + 16)));
+      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16 + 16) + 4));
   /* full-frame per-pass operators are frame-independent: chain them once
    * here (a 3-select pick in the pass loop) instead of a ~96-VALU serial
    * mulmod per pass per frame */
@@ -1976,7 +1997,7 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_reg_k(
           if (int64_t(i) * 4096 + lane16 + 16 <= rbytes) np = i + 1;
         const int64_t end =
             np ? r0 + int64_t(np - 1) * 4096 + lane16 + 16 : r0;
-        op = x8n_d(uint64_t(payload - end));
+        op = x8n_d(uint64_t(payload - end + 4));
       }
 
       const int rbi = int(rbytes);
@@ -2044,7 +2065,7 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_reg_k(
              * dword-aligned dwordx4 (the loads at p0 = f*65532 already
              * run that way), so one store instead of four */
             fstore16<ST>(fdst + off, v);
-            if (SKEL != 1 && SKEL != 3) t = shift4k(t, stab) ^ crc16_reg(v, tab);
+            if (SKEL != 1 && SKEL != 3) t = shift4k(t, stab) ^ crc12u_reg(v, tab);
           }
         }
         uint32_t part = SKEL == 2 ? t : (t ? gf2_mulmod_d(op, t) : 0);
@@ -2115,7 +2136,7 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_reg_k(
           if (off + 16 <= rbi) {
             fstore16<ST>(fdst + off, acc[r][i]);
             if (SKEL != 1 && SKEL != 3)
-              t = shift4k(t, stab) ^ crc16_reg(acc[r][i], tab);
+              t = shift4k(t, stab) ^ crc12u_reg(acc[r][i], tab);
           }
         }
         uint32_t part = SKEL == 2 ? t : (t ? gf2_mulmod_d(op, t) : 0);
@@ -2354,7 +2375,7 @@ GFRS_DEV void al_pin(uint4 &v) {
  * the slab and the coefficient tables) */
 constexpr int AL_LDS_FIXED = 12288 + EF_RED + 64 + 256 + 1024 + 256 + 4096;
 
-template <int GM, int WPS, int SKEL = 0, int ST = 0, int C0 = 0>
+template <int GM, int WPS, int SKEL = 0, int ST = 0, int C0 = 0, int CRC16 = 0>
 __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
     uint8_t *__restrict__ dst, size_t dst_stride, uint64_t base,
     uint64_t stripe_stride, size_t shard_len, int k,
@@ -2404,8 +2425,12 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
    * lane and shard over all 16 pieces (1024 B apart within a pass, 13312 B
    * from piece 3 of a pass to piece 0 of the next), folded once by the
    * suffix after the lane's last piece of pass 3, 16384 - 16*(ql0+193).
+   * The chain is built from crc12u_reg pieces, each short of crc16_reg by
+   * a factor x^32, which commutes through the chain into the operator: 4
+   * bytes more (CRC16 = 1 keeps crc16_reg and the plain suffix).
    * The operator waits in LDS: it is needed once per shard per frame */
-  run0[(k + GM) * 256 + tid] = x8n_d(uint64_t(16384 - 16 * (ql0 + 192 + 1)));
+  run0[(k + GM) * 256 + tid] =
+      x8n_d(uint64_t(16384 - 16 * (ql0 + 192 + 1) + (CRC16 ? 0 : 4)));
   const uint32_t it_full =
       gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
   __syncthreads();
@@ -2527,7 +2552,8 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
               fstore16<ST>(fdst + 16 * q, v);
             }
             if (SKEL != 1)
-              t = (FULL && i == 0 ? t : shift4k(t, stab)) ^ crc16_reg(v, tab);
+              t = (FULL && i == 0 ? t : shift4k(t, stab)) ^
+                  (FULL && !CRC16 ? crc12u_reg(v, tab) : crc16_reg(v, tab));
           }
         };
         piece(std::integral_constant<int, 0>{});
@@ -2592,7 +2618,8 @@ __global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_encode_frame_al_k(
               fstore16<ST>(fdst + 16 * q, v);
             }
             if (SKEL != 1)
-              t = (FULL && i == 0 ? t : shift4k(t, stab)) ^ crc16_reg(v, tab);
+              t = (FULL && i == 0 ? t : shift4k(t, stab)) ^
+                  (FULL && !CRC16 ? crc12u_reg(v, tab) : crc16_reg(v, tab));
           }
         }
         if (FULL) {
@@ -4603,14 +4630,20 @@ void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
   if (var == 79) {
     const int lds =
         AL_LDS_FIXED + (k + (m < 4 ? m : 4) + 1) * 1024 + m * k * 32;
-#define GFRS_AL_GO(G, SK, C)                                             \
-  hipLaunchKernelGGL((rs_encode_frame_al_k<G, 3, SK, 0, C>), dim3(grid2), \
-                     dim3(CRC_BLOCKT), lds, s, dst, dst_stride, base,     \
-                     stripe_stride, shard_len, k, ltabs, total2, fps2,    \
-                     tinyi)
+#define GFRS_AL_GO(G, SK, C, R)                                           \
+  hipLaunchKernelGGL((rs_encode_frame_al_k<G, 3, SK, 0, C, R>),           \
+                     dim3(grid2), dim3(CRC_BLOCKT), lds, s, dst,          \
+                     dst_stride, base, stripe_stride, shard_len, k, ltabs, \
+                     total2, fps2, tinyi)
     /* diagnostics (GM=3 only): GFRS_EF_ABL=4 = memory skeleton (loads,
      * rotation, stores; MAC and CRC compiled out), GFRS_EF_C0=1 = chunk 0
-     * held in LDS and written as one aligned uint4 in the epilogue */
+     * held in LDS and written as one aligned uint4 in the epilogue,
+     * GFRS_EF_CRC16=1 = full frames keep the 16+4-gather piece form
+     * (crc16_reg, operator without the 4 bytes) for a same-build A/B */
+    static const int al_crc16 = []() {
+      const char *e = getenv("GFRS_EF_CRC16");
+      return e ? atoi(e) : 0;
+    }();
     static const int al_abl = []() {
       const char *e = getenv("GFRS_EF_ABL");
       return e ? atoi(e) : 0;
@@ -4619,13 +4652,14 @@ void launch_rs_encode_frame(uint8_t *dst, size_t dst_stride, uint64_t base,
       const char *e = getenv("GFRS_EF_C0");
       return e ? atoi(e) : 0;
     }();
-    if (m == 3 && var_env == 79 && al_abl == 4) { GFRS_AL_GO(3, 1, 0); return; }
-    if (m == 3 && var_env == 79 && al_c0 == 1) { GFRS_AL_GO(3, 0, 1); return; }
+    if (m == 3 && var_env == 79 && al_abl == 4) { GFRS_AL_GO(3, 1, 0, 0); return; }
+    if (m == 3 && var_env == 79 && al_c0 == 1) { GFRS_AL_GO(3, 0, 1, 0); return; }
+    if (m == 3 && var_env == 79 && al_crc16 == 1) { GFRS_AL_GO(3, 0, 0, 1); return; }
     switch (m) {
-      case 1: GFRS_AL_GO(1, 0, 0); break;
-      case 2: GFRS_AL_GO(2, 0, 0); break;
-      case 3: GFRS_AL_GO(3, 0, 0); break;
-      default: GFRS_AL_GO(4, 0, 0);
+      case 1: GFRS_AL_GO(1, 0, 0, 0); break;
+      case 2: GFRS_AL_GO(2, 0, 0, 0); break;
+      case 3: GFRS_AL_GO(3, 0, 0, 0); break;
+      default: GFRS_AL_GO(4, 0, 0, 0);
     }
 #undef GFRS_AL_GO
     return;
