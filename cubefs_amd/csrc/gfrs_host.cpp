@@ -250,6 +250,13 @@ struct gfrs_ctx_impl {
                         the results */
   DevBuf shardwq_buf; /* shard write queue: the same, with the write queue's
                          items and jobs */
+  DevBuf putq_buf; /* put queue: work items, frame prefix sums and image table
+                      of one call (the uploaded blob), then the image CRCs */
+  DevPlan put_lrc; /* put queue, LRC tactics outside lrc_single_pass: the
+                      plan_fused_lrc rows, uploaded by the first put call
+                      (fused_lrc, and every gate that reads fused_lrc_ok, stay
+                      as they are) */
+  bool put_lrc_ok = false;
   DevBuf read_scratch; /* read queue, slow jobs: one decoded stripe of the
                           touched frames; grown on demand, freed with the
                           context */
@@ -1626,7 +1633,7 @@ int gfrs_repair_queue(gfrs_ctx *ctx, void *base, const gfrs_rjob *jobs,
           cd.t.n, b.gm, fail, c->stream);
     launch_shard_finalize_queue((uint8_t *)disk_dst,
                                 (const gfrs_rimage *)(dq + o_imgs),
-                                int(sched.images.size()), c->stream);
+                                int(sched.images.size()), nullptr, c->stream);
     e = hipGetLastError();
   }
   if (rc != GFRS_OK || e != hipSuccess) {
@@ -2028,6 +2035,110 @@ int gfrs_shard_write_queue(gfrs_ctx *ctx, void *dst, const void *src,
   if (e != hipSuccess) return hip_fail("shard_write_queue launch", e);
   if (se != hipSuccess) return hip_fail("shard_write_queue sync", se);
   memcpy(results, back.data(), nres);
+  return GFRS_OK;
+}
+
+/* The put queue: encode + frame + header/footer per job, as one call, for every
+ * tactic up to 32 data shards.  gfrs_plan.cpp validates the jobs and builds
+ * the schedule; this function uploads one blob [work items | frame prefix
+ * sums | image table] through the pinned staging, issues the encode queue's
+ * buckets (narrow tactics) or the two frame buckets once per row group (wide
+ * ones), then the head launch, reads the image CRCs back and syncs once. */
+int gfrs_put_queue(gfrs_ctx *ctx, void *disk_dst, const void *base,
+                   const gfrs_pjob *jobs, int njobs, const uint64_t *vuids,
+                   int nvol, int64_t block_len, uint32_t *crcs) {
+  auto *c = reinterpret_cast<gfrs_ctx_impl *>(ctx);
+  const Code &cd = c->code;
+  const gfrs_tactic &t = cd.t;
+  int rc = put_queue_gate(cd, block_len);
+  if (rc != GFRS_OK) return rc;
+  if (!disk_dst || !base) return GFRS_ERR_INVALID_SHARDS;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamGuard g(c);
+  PutSchedule sched;
+  rc = put_queue_schedule(cd, jobs, njobs, vuids, nvol, (uint64_t)disk_dst,
+                          &sched);
+  if (rc != GFRS_OK) return rc;
+
+  /* the parity rows over the n data shards, row-major [rows*n][32] */
+  const DevPlan *pl = &c->enc_plan;
+  if (t.l > 0) {
+    if (c->fused_lrc_ok) {
+      pl = &c->fused_lrc;
+    } else {
+      if (!c->put_lrc_ok) {
+        Plan p;
+        if ((rc = plan_fused_lrc(cd, &p)) != GFRS_OK) return rc;
+        if ((rc = c->put_lrc.upload(p, c->stream)) != GFRS_OK) return rc;
+        c->put_lrc_ok = true;
+      }
+      pl = &c->put_lrc;
+    }
+  }
+
+  const EncSchedule &es = sched.enc;
+  const size_t nimg = sched.images.size();
+  const size_t o_prefix = es.items.size() * sizeof(gfrs_eitem);
+  const size_t o_imgs = o_prefix + es.frame_prefix.size() * 8;
+  const size_t nblob = o_imgs + nimg * sizeof(gfrs_rimage);
+  const size_t o_crc = nblob;
+  if ((rc = c->putq_buf.ensure(o_crc + nimg * 4)) != GFRS_OK) return rc;
+  uint8_t *dq = (uint8_t *)c->putq_buf.p;
+  /* the staging an async gfrs_shard_write_batch may still upload its ids
+   * from: pin_for_write waits that copy out */
+  uint8_t *blob;
+  if ((rc = pin_for_write(view_of(c), nblob, &blob)) != GFRS_OK) return rc;
+  memcpy(blob, es.items.data(), o_prefix);
+  if (o_imgs > o_prefix)
+    memcpy(blob + o_prefix, es.frame_prefix.data(), o_imgs - o_prefix);
+  memcpy(blob + o_imgs, sched.images.data(), nblob - o_imgs);
+
+  uint8_t *dst = (uint8_t *)disk_dst;
+  const int k = t.n;
+  hipError_t e =
+      hipMemcpyAsync(dq, blob, nblob, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    const uint64_t *dprefix = (const uint64_t *)(dq + o_prefix);
+    if (!sched.wide) {
+      const int gm = t.m + t.l;
+      for (const EncBucket &b : es.buckets) {
+        const gfrs_eitem *items = (const gfrs_eitem *)dq + b.first;
+        if (b.kind == GFRS_EQ_SMALL)
+          launch_rs_encode_frame_small_queue(dst, (uint64_t)base, items,
+                                             uint32_t(b.count), k, gm, b.param,
+                                             pl->tab(), c->stream);
+        else
+          launch_rs_encode_frame_queue(
+              dst, (uint64_t)base, items, dprefix + b.prefix,
+              uint32_t(b.count), es.frame_prefix[b.prefix + b.count], k, gm,
+              pl->tab(), b.param, c->stream);
+      }
+    } else {
+      for (size_t gi = 0; gi < sched.group_rows.size(); gi++) {
+        const int row0 = int(gi) * PUT_ROWS;
+        for (const EncBucket &b : es.buckets)
+          launch_rs_put_frame_queue(
+              dst, (uint64_t)base, (const gfrs_eitem *)dq + b.first,
+              dprefix + b.prefix, uint32_t(b.count),
+              es.frame_prefix[b.prefix + b.count], k, sched.group_rows[gi],
+              row0, pl->tab() + size_t(row0) * k * 32, b.param, gi == 0,
+              c->stream);
+      }
+    }
+    launch_shard_finalize_queue(dst, (const gfrs_rimage *)(dq + o_imgs),
+                                int(nimg), (uint32_t *)(dq + o_crc),
+                                c->stream);
+    e = hipGetLastError();
+  }
+  std::vector<uint32_t> back(crcs ? nimg : 0);
+  if (e == hipSuccess && crcs)
+    e = hipMemcpyAsync(back.data(), dq + o_crc, nimg * 4,
+                       hipMemcpyDeviceToHost, c->stream);
+  hipError_t se = hipStreamSynchronize(c->stream); /* the one sync; the blob
+                                                      is read until here */
+  if (e != hipSuccess) return hip_fail("put_queue launch", e);
+  if (se != hipSuccess) return hip_fail("put_queue sync", se);
+  if (crcs) memcpy(crcs, back.data(), nimg * 4);
   return GFRS_OK;
 }
 

@@ -167,9 +167,26 @@ void launch_rs_repair_frame_queue(uint8_t *dst, uint64_t base,
                                   uint32_t *fail, hipStream_t s);
 /* Headers and footers of every image of a repair queue: launch_shard_finalize
  * with the image's place, raw size and ids read from imgs[]; block_len is
- * 65536. */
+ * 65536.  crcs: NULL, or a device array of nimg words that gets the footer's
+ * CRC of every image (the put queue's read-back). */
 void launch_shard_finalize_queue(uint8_t *dst, const gfrs_rimage *imgs,
-                                 int nimg, hipStream_t s);
+                                 int nimg, uint32_t *crcs, hipStream_t s);
+
+/* Put queue, wide tactics: one frame bucket of the put schedule (gfrs_plan.h)
+ * for one row group.  An item is its own job:
+ *   data shard c at base + item.off + c * item.shard_len, c < k <= 32,
+ *   body of image column j at dst + item.img + j * item.img_stride.
+ * The launch computes gm = 1..4 parity rows from tabs ([gm*k][32], the
+ * group's slice of the plan) into image columns k + row0 + r; data = true
+ * (group 0: row0 must be 0, the DATA build takes it as a constant) also frames
+ * the k data shards into columns 0..k-1, data = false reads them only.
+ * frame_prefix, total_frames and var as for launch_rs_encode_frame_queue. */
+void launch_rs_put_frame_queue(uint8_t *dst, uint64_t base,
+                               const gfrs_eitem *items,
+                               const uint64_t *frame_prefix, uint32_t nitems,
+                               uint64_t total_frames, int k, int gm, int row0,
+                               const uint8_t *tabs, int var, bool data,
+                               hipStream_t s);
 
 /* Read queue: one bucket of the read schedule (gfrs_plan.h), i.e. every work
  * item whose descriptor rebuilds r rows (0..4).  An item reads the frames its

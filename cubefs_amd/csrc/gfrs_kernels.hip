@@ -24,6 +24,7 @@
  */
 #include "gfrs_internal.h"
 
+#include <cassert>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -5217,6 +5218,352 @@ void launch_rs_encode_frame_queue(uint8_t *dst, uint64_t base,
 #undef GFRS_EQ_GO
 }
 
+/* Put queue, wide tactics: rs_encode_frame_queue_k's frame - the grid-stride
+ * walk, the advance map, the cross-item prefetch rule, the 16 KiB passes, the
+ * register CRC, the LDS tail bytes, the header lanes - for one ROW GROUP of a
+ * tactic whose m+l parity rows do not fit one launch, with three changes:
+ *  - k up to PUT_MAX_N = 32: red has PF_SLOTS = 36 words per wave (k data
+ *    slots + 4 parity slots), tailb 16 bytes for each of 32 inputs, ctab up
+ *    to 4*32 coefficients; the header lanes j < k + GM <= 36 still sit in
+ *    wave 0;
+ *  - row0: the GM parity rows of the launch are image columns k + row0 + r,
+ *    and tabs points at the group's slice of the plan;
+ *  - DATA = true is group 0 and stores the data frames and their CRCs as the
+ *    sibling does.  DATA = false is a later group: the data is loaded and
+ *    multiplied only - no data store, no data CRC, no data header word, no
+ *    tail-byte store to the data images (tailb is still filled: the parity
+ *    tail bytes are computed from it).
+ * No lane leaves the frame loop early, no load leaves the data shards of the
+ * item it belongs to, no store leaves the declared images. */
+constexpr int PF_SLOTS = 36;                /* red words per wave */
+constexpr int PF_RED = 4 * PF_SLOTS * 4;    /* bytes */
+constexpr int PF_TAILB = 32 * 16;
+constexpr int PF_LDS_FIXED = 12288 + PF_RED + 64 + PF_TAILB;
+
+template <int GM, int WPS, int ST, bool DATA>
+__global__ __launch_bounds__(CRC_BLOCKT, WPS) void rs_put_frame_queue_k(
+    uint8_t *__restrict__ dst /* disk images */, uint64_t base,
+    const gfrs_eitem *__restrict__ items,
+    const uint64_t *__restrict__ frame_prefix, uint32_t nitems,
+    uint64_t total_frames, int k, int row0,
+    const uint8_t *__restrict__ tabs /* [GM*k][32], the group's slice */) {
+  /* DATA launches are group 0: row0 == 0 (launch_rs_put_frame_queue) */
+  constexpr int EF_PASS = 16384;
+  constexpr int EF_PASSES = 4;
+  constexpr int64_t block_len = 65536;
+  constexpr int64_t payload_full = block_len - CRC_LEN;
+
+  /* block b walks frames b, b + grid, b + 2*grid, ... */
+  const uint64_t f_step = uint64_t(gridDim.x);
+  const uint64_t f_lo = uint64_t(blockIdx.x);
+  const uint64_t f_hi = total_frames;
+  if (f_lo >= f_hi) return; /* whole block, before any barrier */
+  /* group 0 is the DATA launch: its rows start at 0 by construction, and
+   * with the constant the parity image rows continue the data loop's pointer
+   * as in the sibling (a runtime row0 costs the DATA forms two more spilled
+   * VGPRs) */
+  const int prow0 = DATA ? 0 : row0;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t(*tab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem);
+  uint32_t(*stab)[256] = reinterpret_cast<uint32_t(*)[256]>(smem + 8192);
+  uint32_t *red = reinterpret_cast<uint32_t *>(smem + 12288);
+  uint32_t *x8tab = reinterpret_cast<uint32_t *>(smem + 12288 + PF_RED);
+  uint8_t *tailb = smem + 12288 + PF_RED + 64;
+  uint8_t *ctab = smem + PF_LDS_FIXED;
+  for (int i = threadIdx.x; i < 2048; i += CRC_BLOCKT)
+    (&tab[0][0])[i] = (&g_crc_tab4[0][0])[i];
+  for (int i = threadIdx.x; i < 1024; i += CRC_BLOCKT)
+    (&stab[0][0])[i] = (&g_shift4k[0][0])[i];
+  for (int i = threadIdx.x; i < GM * k * 2; i += CRC_BLOCKT)
+    reinterpret_cast<uint4 *>(ctab)[i] =
+        reinterpret_cast<const uint4 *>(tabs)[i];
+  if (threadIdx.x == 0) {
+    uint32_t v = 0x80000000u;
+    for (int j = 0; j < 16; j++) {
+      x8tab[j] = v;
+      v = gf2_mulmod_d(v, g_pow8[0]);
+    }
+  }
+  const int64_t lane16 = int64_t(threadIdx.x) * 16;
+  const int lane16i = int(threadIdx.x) * 16;
+  constexpr uint32_t INV16K = 0x479933FCu;
+  const uint32_t op_pA =
+      x8n_d(uint64_t(payload_full - (3 * 4096 + lane16 + 16)));
+  const uint32_t op_pB = gf2_mulmod_d(op_pA, INV16K);
+  const uint32_t op_pC = gf2_mulmod_d(op_pB, INV16K);
+  const uint32_t op_pD = gf2_mulmod_d(op_pC, INV16K);
+  const uint32_t it_full =
+      gf2_mulmod_d(x8n_d(uint64_t(payload_full)), 0xFFFFFFFFu);
+  __syncthreads();
+
+  /* largest it with frame_prefix[it] <= f_lo (frame_prefix[0] == 0) */
+  uint32_t it = 0;
+  for (uint32_t hi = nitems; hi - it > 1;) {
+    const uint32_t mid = it + (hi - it) / 2;
+    if (frame_prefix[mid] <= f_lo)
+      it = mid;
+    else
+      hi = mid;
+  }
+
+  uint4 vnext[4] = {uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0},
+                    uint4{0, 0, 0, 0}};
+  bool pref = false; /* vnext = pass 0, unit 0 of the frame about to start */
+
+  /* `it` -> the item of frame `to` (>= the frame `it` stands for): gallop,
+   * then bisect; one compare when the frame belongs to the same item */
+  auto advance = [&](uint32_t from, uint64_t to) {
+    if (frame_prefix[from + 1] > to) return from; /* from + 1 <= nitems */
+    uint32_t lo = from + 1, step = 1;
+    while (lo + step < nitems && frame_prefix[lo + step] <= to) {
+      lo += step;
+      step <<= 1;
+    }
+    uint32_t hi = lo + step < nitems ? lo + step : nitems;
+    while (hi - lo > 1) { /* frame_prefix[lo] <= to < frame_prefix[hi] */
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (frame_prefix[mid] <= to)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    return lo;
+  };
+
+  for (uint64_t fr = f_lo; fr < f_hi; fr += f_step) {
+    it = advance(it, fr); /* a no-op after a prefetch */
+    const gfrs_eitem item = items[it];
+    const size_t shard_len = item.shard_len;
+    const int64_t f = int64_t(fr - frame_prefix[it]);
+    const int64_t p0 = f * payload_full;
+    const int64_t payload = i64min(payload_full, int64_t(shard_len) - p0);
+    const uint8_t *sbase = as_global(base + item.off);
+    /* frame f of the body of shard 0's image; column j at + j * img_stride */
+    uint8_t *irow = dst + item.img + f * block_len;
+
+    uint4 acc[GM][4];
+    if (!pref) { /* pass 0, unit 0 */
+      const int rb0 = int(i64min(int64_t(EF_PASS), payload));
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int off = i * 4096 + lane16i;
+        vnext[i] = off + 16 <= rb0
+                       ? *reinterpret_cast<const uint4 *>(sbase + p0 + off)
+                       : uint4{0, 0, 0, 0};
+      }
+    }
+    pref = false;
+    for (int j = threadIdx.x; j < 4 * PF_SLOTS; j += CRC_BLOCKT) red[j] = 0;
+    __syncthreads();
+
+    for (int h = 0; h < EF_PASSES; h++) {
+      const int64_t r0 = int64_t(h) * EF_PASS;
+      const int64_t rbytes = i64min(int64_t(EF_PASS), payload - r0);
+      if (rbytes <= 0) break;
+#pragma unroll
+      for (int r = 0; r < GM; r++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[r][i] = uint4{0, 0, 0, 0};
+
+      uint32_t op = h == 0   ? op_pA
+                    : h == 1 ? op_pB
+                    : h == 2 ? op_pC
+                             : op_pD;
+      if (h == EF_PASSES - 1 && threadIdx.x == 255)
+        op = shift4k(op, stab); /* lane 255's last pass has 3 pieces */
+      if (payload != payload_full) {
+        int np = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (int64_t(i) * 4096 + lane16 + 16 <= rbytes) np = i + 1;
+        const int64_t end =
+            np ? r0 + int64_t(np - 1) * 4096 + lane16 + 16 : r0;
+        op = x8n_d(uint64_t(payload - end));
+      }
+
+      const int rbi = int(rbytes);
+      for (int c = 0; c < k; c++) {
+        const uint8_t *src = sbase + size_t(c) * shard_len + p0 + r0;
+        uint8_t *fdst = irow + size_t(c) * item.img_stride + CRC_LEN + r0;
+        LinTab lt[GM];
+#pragma unroll
+        for (int r = 0; r < GM; r++) lt[r] = lintab_load(ctab, r * k + c);
+        uint4 vcur[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) vcur[i] = vnext[i];
+        if (c + 1 < k) { /* next input's loads fly over this MAC */
+          const uint8_t *nsrc = sbase + size_t(c + 1) * shard_len + p0 + r0;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            vnext[i] = off + 16 <= rbi
+                           ? *reinterpret_cast<const uint4 *>(nsrc + off)
+                           : uint4{0, 0, 0, 0};
+          }
+        }
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int off = i * 4096 + lane16i;
+          if (off + 16 <= rbi) {
+            const uint4 v = vcur[i];
+#pragma unroll
+            for (int d = 0; d < 4; d++)
+              gfmac4_lin_rows<GM>(acc, i, d, (&v.x)[d], lt);
+            if (DATA) {
+              fstore16<ST>(fdst + off, v);
+              t = shift4k(t, stab) ^ crc16_reg(v, tab);
+            }
+          }
+        }
+        uint32_t part = 0;
+        if (DATA) part = t ? gf2_mulmod_d(op, t) : 0;
+        if (rbytes < EF_PASS) { /* lane-parallel tail, one byte per lane */
+          const int t0 = (rbi / 16) * 16;
+          const int p = t0 + int(threadIdx.x);
+          if (p < rbi) {
+            const uint8_t x = src[p];
+            tailb[c * 16 + (p - t0)] = x;
+            if (DATA) {
+              fdst[p] = x;
+              part ^= gf2_mulmod_d(x8tab[rbi - 1 - p], tab[0][x]);
+            }
+          }
+        }
+        if (DATA) {
+#pragma unroll
+          for (int sh = 32; sh > 0; sh >>= 1)
+            part ^= __shfl_xor(part, sh, 64);
+          if ((threadIdx.x & 63) == 0)
+            red[(threadIdx.x >> 6) * PF_SLOTS + c] ^= part;
+        }
+      }
+      if (rbytes < EF_PASS) __syncthreads(); /* tailb visible to all */
+      { /* unit 0 of the next pass, or of the next frame, flies during the
+           parity rows and the frame epilogue */
+        const int64_t r0n = r0 + EF_PASS;
+        int64_t rbn = i64min(int64_t(EF_PASS), payload - r0n);
+        const uint8_t *nbase = sbase + p0 + r0n;
+        if (rbn <= 0 && fr + f_step < f_hi) {
+          /* this block's next frame, from ITS item (the same job or a later
+           * one: its own off and shard_len); `it` moves on with it - the
+           * rest of this frame works on `item` */
+          it = advance(it, fr + f_step);
+          const gfrs_eitem nx = items[it];
+          const int64_t p0n =
+              int64_t(fr + f_step - frame_prefix[it]) * payload_full;
+          rbn = i64min(int64_t(EF_PASS), int64_t(nx.shard_len) - p0n);
+          nbase = as_global(base + nx.off) + p0n;
+          pref = true;
+        }
+        if (rbn > 0) {
+          const int rbni = int(rbn);
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int off = i * 4096 + lane16i;
+            vnext[i] = off + 16 <= rbni
+                           ? *reinterpret_cast<const uint4 *>(nbase + off)
+                           : uint4{0, 0, 0, 0};
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < GM; r++) {
+        uint8_t *fdst =
+            irow + size_t(k + prow0 + r) * item.img_stride + CRC_LEN + r0;
+        uint32_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int off = i * 4096 + lane16i;
+          if (off + 16 <= rbi) {
+            fstore16<ST>(fdst + off, acc[r][i]);
+            t = shift4k(t, stab) ^ crc16_reg(acc[r][i], tab);
+          }
+        }
+        uint32_t part = t ? gf2_mulmod_d(op, t) : 0;
+        if (rbytes < EF_PASS) {
+          const int t0 = (rbi / 16) * 16;
+          const int p = t0 + int(threadIdx.x);
+          if (p < rbi) {
+            uint8_t pv = 0;
+            for (int c2 = 0; c2 < k; c2++) {
+              const uint8_t b = tailb[c2 * 16 + (p - t0)];
+              pv ^= gfmul1_lin(ctab + size_t(r * k + c2) * 32, b);
+            }
+            fdst[p] = pv;
+            part ^= gf2_mulmod_d(x8tab[rbi - 1 - p], tab[0][pv]);
+          }
+        }
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1)
+          part ^= __shfl_xor(part, sh, 64);
+        if ((threadIdx.x & 63) == 0)
+          red[(threadIdx.x >> 6) * PF_SLOTS + k + r] ^= part;
+      }
+    }
+
+    __syncthreads();
+    { /* one frame-header lane per image column of the launch: the k data
+         columns (DATA only) and the GM parity columns; j < k + GM <= 36, all
+         in wave 0 */
+      const int j = int(threadIdx.x);
+      if (j < k + GM && (DATA || j >= k)) {
+        const uint32_t itv =
+            payload == payload_full
+                ? it_full
+                : gf2_mulmod_d(x8n_d(uint64_t(payload)), 0xFFFFFFFFu);
+        const uint32_t crc =
+            ~(itv ^ red[j] ^ red[PF_SLOTS + j] ^ red[2 * PF_SLOTS + j] ^
+              red[3 * PF_SLOTS + j]);
+        const int col = j < k ? j : j + prow0;
+        *reinterpret_cast<uint32_t *>(irow + size_t(col) * item.img_stride) =
+            crc;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+void launch_rs_put_frame_queue(uint8_t *dst, uint64_t base,
+                               const gfrs_eitem *items,
+                               const uint64_t *frame_prefix, uint32_t nitems,
+                               uint64_t total_frames, int k, int gm, int row0,
+                               const uint8_t *tabs, int var, bool data,
+                               hipStream_t s) {
+  if (nitems == 0 || total_frames == 0) return;
+  assert(!data || row0 == 0); /* the DATA build takes row0 as the constant 0 */
+  /* the grid rule of launch_rs_encode_frame_queue */
+  const uint64_t cap = uint64_t(env_grid("GFRS_CRC_GRID", 16384));
+  int grid = int(total_frames < cap ? total_frames : cap);
+  const int lds = PF_LDS_FIXED + gm * k * 32;
+  if (uint64_t(grid) < total_frames && grid >= 1024) {
+    auto gcd = [](int a, int b) {
+      while (b) { const int t2 = a % b; a = b; b = t2; }
+      return a;
+    };
+    while (gcd(grid, 2 * 3 * 5 * 7 * 11 * 13) != 1) grid--;
+  }
+#define GFRS_PQ_GO(G, W, S, D)                                             \
+  hipLaunchKernelGGL((rs_put_frame_queue_k<G, W, S, D>), dim3(grid),       \
+                     dim3(CRC_BLOCKT), lds, s, dst, base, items,           \
+                     frame_prefix, nitems, total_frames, k, row0, tabs)
+#define GFRS_PQ_SW(W, S, D)                                                \
+  switch (gm) {                                                            \
+    case 1: GFRS_PQ_GO(1, W, S, D); break;                                 \
+    case 2: GFRS_PQ_GO(2, W, S, D); break;                                 \
+    case 3: GFRS_PQ_GO(3, W, S, D); break;                                 \
+    default: GFRS_PQ_GO(4, W, S, D);                                       \
+  }
+  if (var == 76) {
+    if (data) { GFRS_PQ_SW(3, 0, true) } else { GFRS_PQ_SW(3, 0, false) }
+  } else {
+    if (data) { GFRS_PQ_SW(4, 1, true) } else { GFRS_PQ_SW(4, 1, false) }
+  }
+#undef GFRS_PQ_SW
+#undef GFRS_PQ_GO
+}
+
 /* Encode+frame queue, small class: rs_encode_frame_small_k with the stripe
  * loop turned into a loop over the items of one small bucket, wave
  * 4*blockIdx + wv, grid-stride.  Every item of the bucket has
@@ -5532,10 +5879,12 @@ void launch_shard_finalize(uint8_t *dst, size_t dst_stride,
 }
 
 /* shard_finalize_k for a repair queue: one wave per image, its place, raw
- * size and ids read from the image table (block_len 65536). */
+ * size and ids read from the image table (block_len 65536).  crcs (the put
+ * queue's; NULL for the repair queue) also gets the footer's value of image
+ * sh at crcs[sh]. */
 __global__ void shard_finalize_queue_k(uint8_t *__restrict__ dst,
                                        const gfrs_rimage *__restrict__ imgs,
-                                       int nimg) {
+                                       int nimg, uint32_t *__restrict__ crcs) {
   constexpr int64_t block_len = 65536;
   const int sh = blockIdx.x * (blockDim.x / 64) + (threadIdx.x / 64);
   const int lane = threadIdx.x & 63;
@@ -5591,15 +5940,16 @@ __global__ void shard_finalize_queue_k(uint8_t *__restrict__ dst,
   ftr[0] = 0xcc; ftr[1] = 0xef; ftr[2] = 0xcd; ftr[3] = 0xab;
   ftr[4] = uint8_t(crc >> 24); ftr[5] = uint8_t(crc >> 16); /* BE */
   ftr[6] = uint8_t(crc >> 8); ftr[7] = uint8_t(crc);
+  if (crcs) crcs[sh] = crc;
 }
 
 void launch_shard_finalize_queue(uint8_t *dst, const gfrs_rimage *imgs,
-                                 int nimg, hipStream_t s) {
+                                 int nimg, uint32_t *crcs, hipStream_t s) {
   if (nimg <= 0) return;
   const int wps = 4; /* waves per block */
   const int blocks = (nimg + wps - 1) / wps;
   hipLaunchKernelGGL(shard_finalize_queue_k, dim3(blocks), dim3(wps * 64), 0,
-                     s, dst, imgs, nimg);
+                     s, dst, imgs, nimg, crcs);
 }
 
 void launch_shard_parse(const uint8_t *img, size_t stride, int64_t raw_size,

@@ -569,25 +569,18 @@ int encode_queue_block_check(int64_t block_len) {
   return block_len == REPAIR_BLOCK ? GFRS_OK : GFRS_ERR_UNSUPPORTED;
 }
 
-int encode_queue_schedule(const gfrs_ejob *jobs, int njobs,
-                          uint64_t framed_addr, EncSchedule *out) {
-  *out = EncSchedule();
-  if (njobs <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
+/* the buckets, items and prefix sums of validated jobs; frame_only puts the
+ * jobs of the small class into the frame bucket below ENCQ_LARGE_MIN (the put
+ * queue's wide tactics) */
+static void encode_queue_fill(const gfrs_ejob *jobs, int njobs,
+                              bool frame_only, EncSchedule *out) {
   /* slots 0..3: small NI 1..4; 4: frame below ENCQ_LARGE_MIN; 5: from it up */
-  auto slot_of = [](uint64_t len) {
-    if (len <= ENCQ_SMALL_MAX) return int((len - 1) / 1024);
+  auto slot_of = [frame_only](uint64_t len) {
+    if (len <= ENCQ_SMALL_MAX && !frame_only) return int((len - 1) / 1024);
     return len < ENCQ_LARGE_MIN ? 4 : 5;
   };
   size_t count[ENCQ_BUCKETS] = {0};
-  for (int j = 0; j < njobs; j++) {
-    const gfrs_ejob &jb = jobs[j];
-    if (jb.reserved != 0) return GFRS_ERR_INVALID_SHARDS;
-    if (jb.shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
-    if ((framed_addr + jb.img_off) % 4 || jb.img_stride % 4 ||
-        jb.img_stride < encode_image_size(jb.shard_len))
-      return GFRS_ERR_INVALID_SHARDS;
-    count[slot_of(jb.shard_len)]++;
-  }
+  for (int j = 0; j < njobs; j++) count[slot_of(jobs[j].shard_len)]++;
   size_t fill[ENCQ_BUCKETS], pre[ENCQ_BUCKETS] = {0}, nitems = 0, npre = 0;
   for (int s = 0; s < ENCQ_BUCKETS; s++) {
     fill[s] = nitems;
@@ -619,6 +612,21 @@ int encode_queue_schedule(const gfrs_ejob *jobs, int njobs,
           out->frame_prefix[pi] + (jb.shard_len - 1) / REPAIR_PAYLOAD + 1;
     }
   }
+}
+
+int encode_queue_schedule(const gfrs_ejob *jobs, int njobs,
+                          uint64_t framed_addr, EncSchedule *out) {
+  *out = EncSchedule();
+  if (njobs <= 0 || !jobs) return GFRS_ERR_INVALID_SHARDS;
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_ejob &jb = jobs[j];
+    if (jb.reserved != 0) return GFRS_ERR_INVALID_SHARDS;
+    if (jb.shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
+    if ((framed_addr + jb.img_off) % 4 || jb.img_stride % 4 ||
+        jb.img_stride < encode_image_size(jb.shard_len))
+      return GFRS_ERR_INVALID_SHARDS;
+  }
+  encode_queue_fill(jobs, njobs, false, out);
   return GFRS_OK;
 }
 
@@ -860,9 +868,88 @@ int shard_write_schedule(const gfrs_wjob *jobs, int njobs, uint64_t dst_addr,
   return GFRS_OK;
 }
 
+/* ---- the put queue ---- */
+
+int put_queue_gate(const Code &c, int64_t block_len) {
+  int rc = encode_queue_block_check(block_len);
+  if (rc != GFRS_OK) return rc;
+  return c.t.m >= 1 && c.t.n <= PUT_MAX_N ? GFRS_OK : GFRS_ERR_UNSUPPORTED;
+}
+
+int put_queue_schedule(const Code &c, const gfrs_pjob *jobs, int njobs,
+                       const uint64_t *vuids, int nvol, uint64_t dst_addr,
+                       PutSchedule *out) {
+  *out = PutSchedule();
+  if (njobs <= 0 || nvol <= 0 || !jobs || !vuids)
+    return GFRS_ERR_INVALID_SHARDS;
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_pjob &jb = jobs[j];
+    if (jb.reserved != 0 || jb.vol < 0 || jb.vol >= nvol)
+      return GFRS_ERR_INVALID_SHARDS;
+    if (jb.shard_len == 0) return GFRS_ERR_SHARD_NO_DATA;
+    if (jb.shard_len >> 32) return GFRS_ERR_INVALID_SHARDS;
+    if ((dst_addr + jb.img_off) % 4 || jb.img_stride % 4 ||
+        jb.img_stride < repair_image_size(jb.shard_len))
+      return GFRS_ERR_INVALID_SHARDS;
+  }
+  const int rows = c.t.m + c.t.l;
+  out->wide = !encode_frame_fused(c);
+  for (int r = 0; r < rows; r += PUT_ROWS)
+    out->group_rows.push_back(rows - r < PUT_ROWS ? rows - r : PUT_ROWS);
+  /* the body of an image is an encode-queue image 32 bytes in */
+  std::vector<gfrs_ejob> ej;
+  ej.resize(size_t(njobs));
+  out->images.reserve(size_t(njobs) * c.total);
+  for (int j = 0; j < njobs; j++) {
+    const gfrs_pjob &jb = jobs[j];
+    ej[j] = gfrs_ejob{jb.off, jb.shard_len, jb.img_off + 32, jb.img_stride, 0};
+    for (int i = 0; i < c.total; i++)
+      out->images.push_back(
+          gfrs_rimage{jb.img_off + uint64_t(i) * jb.img_stride, jb.shard_len,
+                      jb.bid, vuids[size_t(jb.vol) * c.total + i]});
+  }
+  encode_queue_fill(ej.data(), njobs, out->wide, &out->enc);
+  return GFRS_OK;
+}
+
 }  // namespace gfrs
 
 /* ---- GPU-free diagnostic export (include/gfrs.h) ---- */
+
+extern "C" int gfrs_compute_put_queue_schedule(
+    const gfrs_tactic *t, const gfrs_pjob *jobs, int njobs,
+    const uint64_t *vuids, int nvol, int64_t block_len, int item_cap,
+    int image_cap, gfrs_eitem *items, uint64_t *frame_prefix, int *nitems,
+    gfrs_ebucket *buckets, int *nbuckets, gfrs_rimage *images, int *nimages,
+    int *wide, int *ngroups, int32_t *group_rows) {
+  using namespace gfrs;
+  if (!tactic_valid(t)) return GFRS_ERR_INVALID_CODEMODE;
+  Code c;
+  c.t = *t; /* the gate reads the tactic only */
+  int rc = put_queue_gate(c, block_len);
+  if (rc != GFRS_OK) return rc;
+  if (!code_build(*t, &c)) return GFRS_ERR_SINGULAR;
+  PutSchedule s;
+  if ((rc = put_queue_schedule(c, jobs, njobs, vuids, nvol, 0, &s)) != GFRS_OK)
+    return rc;
+  if (s.enc.items.size() > size_t(item_cap < 0 ? 0 : item_cap) ||
+      s.images.size() > size_t(image_cap < 0 ? 0 : image_cap))
+    return GFRS_ERR_NOMEM;
+  *nitems = int(s.enc.items.size());
+  *nbuckets = int(s.enc.buckets.size());
+  *nimages = int(s.images.size());
+  *wide = s.wide ? 1 : 0;
+  *ngroups = int(s.group_rows.size());
+  std::copy(s.enc.items.begin(), s.enc.items.end(), items);
+  std::copy(s.enc.frame_prefix.begin(), s.enc.frame_prefix.end(), frame_prefix);
+  std::copy(s.images.begin(), s.images.end(), images);
+  std::copy(s.group_rows.begin(), s.group_rows.end(), group_rows);
+  for (size_t b = 0; b < s.enc.buckets.size(); b++)
+    buckets[b] = gfrs_ebucket{s.enc.buckets[b].kind, s.enc.buckets[b].param,
+                              int32_t(s.enc.buckets[b].first),
+                              int32_t(s.enc.buckets[b].count)};
+  return GFRS_OK;
+}
 
 extern "C" int gfrs_compute_shard_write_queue_schedule(
     const gfrs_wjob *jobs, int njobs, int64_t block_len, int item_cap,

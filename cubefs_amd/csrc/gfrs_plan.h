@@ -414,6 +414,34 @@ struct ShardWriteSchedule {
 int shard_write_schedule(const gfrs_wjob *jobs, int njobs, uint64_t dst_addr,
                          ShardWriteSchedule *out);
 
+/* ---- the put queue (gfrs_put_queue) ----
+ * The encode+frame queue into disk images, for every tactic up to PUT_MAX_N
+ * data shards.  A job is one work item of the encode schedule whose image row
+ * starts behind the 32-byte header (img = img_off + 32).  The m+l parity rows
+ * - the encode plan's, or plan_fused_lrc's for an LRC tactic - run in row
+ * groups of PUT_ROWS: group g is rows [PUT_ROWS*g, PUT_ROWS*g + rows(g)).  A
+ * tactic inside encode_frame_fused is NARROW: one group, the encode queue's
+ * buckets and kernels.  Every other one is WIDE: only the two frame buckets,
+ * each launched once per group with the put frame kernel.  The image table
+ * (job-major, shard order) feeds the head launch. */
+constexpr int PUT_ROWS = 4;   /* rows per group (the kernels' GM) */
+constexpr int PUT_MAX_N = 32; /* data shards the put frame kernel's LDS holds */
+
+struct PutSchedule {
+  EncSchedule enc;
+  std::vector<gfrs_rimage> images;
+  bool wide = false;
+  std::vector<int32_t> group_rows;
+};
+
+/* block_len and tactic width: GFRS_ERR_INVALID_BLOCK / _UNSUPPORTED */
+int put_queue_gate(const Code &c, int64_t block_len);
+/* Job validation (gfrs.h, put-queue contract; dst_addr = the address of
+ * disk_dst, for the alignment rule) and the schedule. */
+int put_queue_schedule(const Code &c, const gfrs_pjob *jobs, int njobs,
+                       const uint64_t *vuids, int nvol, uint64_t dst_addr,
+                       PutSchedule *out);
+
 }  // namespace gfrs
 
 #endif

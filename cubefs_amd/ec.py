@@ -255,6 +255,36 @@ class Encoder:
                                             block_len),
               "encode_frame_queue")
 
+    def put_queue(self, disk_dst, batch, jobs, vuids, block_len=65536):
+        """Put queue: encode every job straight into the n+m+l disk images
+        blobnode writes - header, crc32block body, footer - in one call, for
+        every tactic up to n = 32 (more than 4 parity rows run in row groups
+        of 4).  batch: flat uint8 device tensor holding the data shards;
+        disk_dst: flat uint8 device tensor for the images; jobs: [(off,
+        shard_len, img_off, img_stride, bid, vol)], data shard i of a job at
+        byte off + i*shard_len of batch, the disk image of its shard i at
+        byte img_off + i*img_stride of disk_dst; vuids: [[n+m+l vuids]], one
+        list per volume, a job's headers carrying vuids[vol].  Blocks until
+        the images are ready and returns the CRC32-IEEE of every raw shard
+        (the shard meta's Crc) as a numpy uint32 array of shape
+        (njobs, n+m+l)."""
+        assert batch.is_cuda and batch.is_contiguous()
+        assert disk_dst.is_cuda and disk_dst.is_contiguous()
+        nj, total = len(jobs), self.tactic.total
+        pj = (runtime.PJob * max(1, nj))()
+        for j, (off, ln, img_off, img_stride, bid, vol) in enumerate(jobs):
+            pj[j] = runtime.PJob(off, ln, img_off, img_stride, bid, vol, 0)
+        flat = [v for vol in vuids for v in vol]
+        assert len(flat) == len(vuids) * total
+        vu = (ctypes.c_uint64 * max(1, len(flat)))(*flat)
+        crcs = np.zeros((max(1, nj), total), dtype=np.uint32)
+        check(lib().gfrs_put_queue(
+            self._ctx, disk_dst.data_ptr(), batch.data_ptr(), pj, nj, vu,
+            len(vuids), block_len,
+            crcs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+            "put_queue")
+        return crcs[:nj]
+
     def verify_batch(self, batch):
         p, ln, stride, ns = self._base(batch)
         nwords = (ns + 63) // 64

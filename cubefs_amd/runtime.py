@@ -295,6 +295,19 @@ class WBucket(ctypes.Structure):
     ]
 
 
+class PJob(ctypes.Structure):
+    """gfrs_pjob: one job of a put queue."""
+    _fields_ = [
+        ("off", ctypes.c_uint64),
+        ("shard_len", ctypes.c_uint64),
+        ("img_off", ctypes.c_uint64),
+        ("img_stride", ctypes.c_uint64),
+        ("bid", ctypes.c_uint64),
+        ("vol", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -441,6 +454,14 @@ def lib():
             ctypes.POINTER(WJob), ctypes.c_int, i64, ctypes.c_int,
             ctypes.POINTER(WItem), u64p, ip, ctypes.POINTER(WBucket), ip,
             u64p]
+        L.gfrs_put_queue.argtypes = [vp, vp, vp, ctypes.POINTER(PJob),
+                                     ctypes.c_int, u64p, ctypes.c_int, i64,
+                                     u32p]
+        L.gfrs_compute_put_queue_schedule.argtypes = [
+            ctypes.POINTER(Tactic), ctypes.POINTER(PJob), ctypes.c_int, u64p,
+            ctypes.c_int, i64, ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(EItem), u64p, ip, ctypes.POINTER(EBucket), ip,
+            ctypes.POINTER(RImage), ip, ip, ip, i32p]
         _lib = L
     return _lib
 

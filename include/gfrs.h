@@ -827,6 +827,79 @@ int gfrs_shard_write_queue(gfrs_ctx *ctx, void *dst, const void *src,
                            const gfrs_wjob *jobs, int njobs, int64_t block_len,
                            gfrs_sresult *results /* njobs, host */);
 
+/* ---- put queue (stream_put.go:146 + datafile.go:342-384: the PUT path from
+ * the blob's data shards to what blobnode writes, over concurrent blobs of
+ * different sizes) ----
+ * gfrs_encode_frame_queue and gfrs_shard_write_queue in one pass, for every
+ * tactic up to n = 32: every job names its n data shards, the place of its
+ * n+m+l disk images, a bid and a vuid set, and gets back the images - header,
+ * crc32block body, footer - and the CRC32-IEEE of every raw shard, the shard
+ * meta's Crc.  jobs, vuids and crcs are host memory, base and disk_dst device
+ * pointers.
+ *
+ * Put-queue contract (pinned by tests/test_gpu_put_queue.py):
+ *  - Per-job result.  Image i of job j (at disk_dst + img_off + i*img_stride,
+ *    gfrs_shard_disk_size(shard_len, 65536) bytes) is byte-identical to the
+ *    reference's shard write of shard i of the job's encoded stripe - the
+ *    reference's Encode of the n data shards, local parities included - with
+ *    bid, vuids[vol*(n+m+l) + i] and size = shard_len: header, freshly
+ *    computed frame CRCs, payload, footer.  crcs[j*(n+m+l) + i] is the
+ *    CRC32-IEEE of that raw shard (shard.Crc of datafile.go:379, the footer's
+ *    value).
+ *  - Layout.  Sources need no alignment.  disk_dst + img_off and img_stride
+ *    are multiples of 4.  In disk_dst only the declared images are written:
+ *    nothing between images, nothing past an image's disk size.  base is never
+ *    written, for any tactic (gfrs_encode_frame_queue writes the parity there
+ *    on its slow tactics; this call has none).  Only the n data shards of each
+ *    job are read: the m+l parity places of the ec.Buffer layout need not
+ *    exist behind them.  Overlapping images, or base overlapping disk_dst, are
+ *    caller errors (not checked).
+ *  - Validation.  Everything is validated before the first launch, and any
+ *    error returns its code and writes nothing, neither in disk_dst nor in
+ *    crcs:
+ *      GFRS_ERR_INVALID_BLOCK for block_len <= 0 or not a multiple of 4096;
+ *      GFRS_ERR_UNSUPPORTED for any other block_len != 65536, for m == 0 and
+ *      for n > 32;
+ *      GFRS_ERR_SHARD_NO_DATA for shard_len == 0;
+ *      GFRS_ERR_INVALID_SHARDS for njobs <= 0, nvol <= 0, vol out of range,
+ *      reserved != 0, shard_len >= 2^32, a misaligned disk_dst + img_off or
+ *      img_stride, or img_stride below the disk size.
+ *  - Blocking.  The call blocks until the images and crcs are ready; it runs
+ *    on the context stream, takes the context mutex once and makes one upload
+ *    of one blob, one read-back (none when crcs is NULL) and one sync.  (The
+ *    first call of an LRC context outside the gate below also uploads its
+ *    composed plan once.)  It obeys the ordering contract above: its upload
+ *    waits out an id upload that an async gfrs_shard_write_batch left queued.
+ *  - Launch bound.  The m+l parity rows run in G = ceil((m+l)/4) row groups
+ *    of 4 rows (the last one of the rest).  A tactic inside the gate of
+ *    gfrs_encode_frame_batch (G = 1, n+m+l <= 16) costs at most 6 + 1
+ *    launches: the buckets of gfrs_encode_frame_queue, then one launch of one
+ *    wave per image that writes header and footer and the crc.  Every other
+ *    tactic costs at most 2*G + 1: per row group the two frame variants (below
+ *    1 MiB per shard / from 1 MiB up); group 0 stores the data frames, a later
+ *    group reads the data again and stores its parity frames only.
+ *  - Limits.  On a tactic outside that gate a job of at most 4096 bytes runs
+ *    the frame kernel, one workgroup per job per group: it is not packed into
+ *    a wave.  The footer CRC is folded serially over the image's frames. */
+typedef struct gfrs_pjob {
+  uint64_t off;        /* data shard i at base + off + i*shard_len, i < n; no
+                          alignment */
+  uint64_t shard_len;  /* 1 .. 2^32-1 */
+  uint64_t img_off;    /* disk image of shard i at
+                          disk_dst + img_off + i*img_stride, i < n+m+l */
+  uint64_t img_stride; /* multiple of 4, >= gfrs_shard_disk_size(shard_len,
+                          65536) */
+  uint64_t bid;        /* written into all n+m+l headers of the job */
+  int32_t vol;         /* 0 <= vol < nvol: header of shard i carries
+                          vuids[vol*(n+m+l) + i] */
+  int32_t reserved;    /* must be 0 */
+} gfrs_pjob;
+
+int gfrs_put_queue(gfrs_ctx *ctx, void *disk_dst, const void *base,
+                   const gfrs_pjob *jobs, int njobs, const uint64_t *vuids,
+                   int nvol, int64_t block_len,
+                   uint32_t *crcs /* njobs*(n+m+l), host, may be NULL */);
+
 /* ---- ec.Buffer size math (buf.go:67-133) ---- */
 int gfrs_buffer_sizes(const gfrs_tactic *t, int64_t data_size,
                       int64_t *shard_size, int64_t *ec_data_size,
@@ -1064,6 +1137,29 @@ int gfrs_compute_shard_write_queue_schedule(
     const gfrs_wjob *jobs, int njobs, int64_t block_len, int item_cap,
     gfrs_witem *items, uint64_t *frame_prefix, int *nitems,
     gfrs_wbucket *buckets, int *nbuckets, uint64_t *total_frames);
+/* GPU-free: what gfrs_put_queue would upload for a queue, with the same
+ * builder, so CPU tests can check it without a device.
+ *   Work items: one gfrs_eitem per job, img = img_off + 32 - the body starts
+ *   behind the header, so the frame kernels see an ordinary 4-aligned image
+ *   row.  *wide = 0: the tactic passes the gate of the fused encode kernels
+ *   and the buckets are those of gfrs_compute_encode_queue_schedule.
+ *   *wide = 1: only the two frame buckets exist (87 below 1 MiB per shard, 76
+ *   from it up), every job in one of them by its length, and the engine
+ *   launches each once per row group.  Prefix sums as in the encode queue.
+ *   Row groups: *ngroups = ceil((m+l)/4); group g carries group_rows[g] rows
+ *   from parity row 4*g on: 4, the last one (m+l) - 4*(*ngroups - 1).
+ *   Image table: one entry per image, job-major and in shard order within a
+ *   job: byte offset in disk_dst, raw size, bid, vuids[vol*(n+m+l) + i].
+ * items holds item_cap entries, frame_prefix item_cap + 2, buckets 6, images
+ * image_cap, group_rows ceil((m+l)/4) (GFRS_ERR_NOMEM when the schedule is
+ * larger).  Returns GFRS_ERR_INVALID_CODEMODE for an invalid tactic, else the
+ * validation codes of gfrs_put_queue, taking disk_dst as 4-aligned. */
+int gfrs_compute_put_queue_schedule(
+    const gfrs_tactic *t, const gfrs_pjob *jobs, int njobs,
+    const uint64_t *vuids, int nvol, int64_t block_len, int item_cap,
+    int image_cap, gfrs_eitem *items, uint64_t *frame_prefix, int *nitems,
+    gfrs_ebucket *buckets, int *nbuckets, gfrs_rimage *images, int *nimages,
+    int *wide, int *ngroups, int32_t *group_rows);
 /* Device probe used by tests: returns 1 when v_perm byte-select semantics
  * match the kernel's assumption (sel>=8 yields 0), 0 otherwise, <0 error. */
 int gfrs_probe_perm(void);

@@ -71,6 +71,18 @@ and gfrs_shard_write_queue (--only xyz), in the same form:
      shards of that size; a read queue and a write batch of its images), a
      sync each.
 
+and gfrs_put_queue (--only ABC), three interleaved medians of queue and
+yardstick each, every yardstick built from the earlier entry points only:
+
+ (A) RS(6+3)  1024 jobs x 8 MiB: the queue vs gfrs_encode_frame_queue, the
+     same kernels without the 9216 head-wave items.
+ (B) EC6P6 and EC15P12, 512 jobs x 4 MiB: the queue vs the only composition
+     that yielded disk images before it - gfrs_encode_batch, then
+     gfrs_shard_write_queue with one raw job per shard - and, beside it,
+     gfrs_encode_frame_queue's slow path (no headers).
+ (C) EC15P12, the 4096-job size mix of (b): the queue vs one such composition
+     per distinct size.
+
 (a) and (d) run on random data with encoded parity; the others on a zeroed buffer
 (a valid stripe: zero parity), since the kernels' work does not depend on
 the data.  One JSON line on stdout; --out also writes it to a file.
@@ -923,6 +935,137 @@ class ShardWriteProbe(ShardProbe):
                                                           check), reps)
 
 
+class PutProbe:
+    """gfrs_put_queue against the calls that were there before it, on zeroed
+    sources.  Every yardstick ends with gfrs_synchronize (or is a blocking
+    queue call) and runs the earlier entry points only."""
+
+    def __init__(self, name):
+        self.t = codemode.get_tactic(name)
+        self.enc = ec.Encoder(self.t)
+        self.L = runtime.lib()
+        self.total = self.t.N + self.t.M + self.t.L
+        self.vuids = (ctypes.c_uint64 * self.total)(*range(100, 100 + self.total))
+
+    def layout(self, lens):
+        """ec.Buffer stripes back to back (the yardsticks encode in place;
+        the put queue reads the n data shards of each); disk images back to
+        back at the tight 4-aligned stride."""
+        jobs, off, img = [], 0, 0
+        for ln in lens:
+            stride = (self.L.gfrs_shard_disk_size(ln, 65536) + 3) // 4 * 4
+            jobs.append((off, ln, img, stride))
+            off += self.total * ln
+            img += self.total * stride
+        return jobs, off, img
+
+    def put(self, buf, dst, pj, crcs):
+        rc = self.L.gfrs_put_queue(self.enc._ctx, dst.data_ptr(),
+                                   buf.data_ptr(), pj, len(pj), self.vuids, 1,
+                                   65536, crcs)
+        assert rc == 0, rc
+
+    def encode_queue(self, buf, dst, ej):
+        rc = self.L.gfrs_encode_frame_queue(self.enc._ctx, dst.data_ptr(),
+                                            buf.data_ptr(), ej, len(ej), 65536)
+        assert rc == 0, rc
+
+    def wjobs(self, groups):
+        """One raw gfrs_wjob per shard of every stripe.  groups: ((off, ln,
+        img, stride), nstripes), stripes and images back to back."""
+        specs = []
+        for (off, ln, img, stride), n in groups:
+            for s in range(n):
+                for i in range(self.total):
+                    specs.append((off + (s * self.total + i) * ln, ln,
+                                  img + (s * self.total + i) * stride, s))
+        wj = (runtime.WJob * len(specs))()
+        for k, (src, ln, im, bid) in enumerate(specs):
+            wj[k] = runtime.WJob(src, ln, bid, 100 + k % self.total, 0, 0, im,
+                                 0, 0)
+        return wj, (runtime.SResult * len(specs))()
+
+    def composition(self, buf, dst, groups, wj, wres):
+        """gfrs_encode_batch per size, then ONE gfrs_shard_write_queue."""
+        for (off, ln, _, _), n in groups:
+            rc = self.L.gfrs_encode_batch(self.enc._ctx, buf.data_ptr() + off,
+                                          ln, self.total * ln, n)
+            assert rc == 0, rc
+        rc = self.L.gfrs_shard_write_queue(self.enc._ctx, dst.data_ptr(),
+                                           buf.data_ptr(), wj, len(wj), 65536,
+                                           wres)
+        assert rc == 0, rc
+        self.enc.synchronize()
+
+    def run(self, lens, reps, narrow):
+        """narrow: the yardstick is gfrs_encode_frame_queue (same kernels, no
+        header, footer or crc).  Otherwise: one composition per distinct size
+        (gfrs_encode_batch, then gfrs_shard_write_queue with one raw job per
+        shard - the only way to the disk images before this call), and beside
+        it gfrs_encode_frame_queue's slow path, which yields no headers."""
+        jobs, nbytes, nimg = self.layout(lens)
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        dst = torch.empty(nimg, dtype=torch.uint8, device="cuda")
+        pj = (runtime.PJob * len(jobs))()
+        ej = (runtime.EJob * len(jobs))()
+        for j, (off, ln, img, stride) in enumerate(jobs):
+            pj[j] = runtime.PJob(off, ln, img, stride, j, 0, 0)
+            ej[j] = runtime.EJob(off, ln, img, stride, 0)
+        crcs = (ctypes.c_uint32 * (len(jobs) * self.total))()
+        res = {"tactic": "%d+%d+%d" % (self.t.N, self.t.M, self.t.L),
+               "njobs": len(jobs), "sizes": len(set(lens)),
+               "data_GB": round(sum(lens) * self.t.N / 1e9, 3),
+               "image_GB": round(nimg / 1e9, 3)}
+        queue = lambda: self.put(buf, dst, pj, crcs)        # noqa: E731
+        if narrow:
+            yard = lambda: self.encode_queue(buf, dst, ej)  # noqa: E731
+        else:
+            # regrouped by size over the same buffers: the same bytes
+            groups, off, img = [], 0, 0
+            for ln in sorted(set(lens)):
+                n = lens.count(ln)
+                stride = (self.L.gfrs_shard_disk_size(ln, 65536) + 3) // 4 * 4
+                groups.append(((off, ln, img, stride), n))
+                off += n * self.total * ln
+                img += n * self.total * stride
+            wj, wres = self.wjobs(groups)
+            yard = lambda: self.composition(buf, dst, groups, wj,  # noqa: E731
+                                            wres)
+        for i in (1, 2, 3):
+            res["yardstick_%d" % i] = timed(yard, reps)
+            res["queue_%d" % i] = timed(queue, reps)
+        ys = [res["yardstick_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        qs = [res["queue_%d" % i]["median_ms"] for i in (1, 2, 3)]
+        res["yardstick_medians_ms"], res["queue_medians_ms"] = ys, qs
+        res["yardstick_spread"] = round(max(ys) / min(ys) - 1, 4)
+        res["queue_spread"] = round(max(qs) / min(qs) - 1, 4)
+        res["queue_over_yardstick"] = round(statistics.median(qs) /
+                                            statistics.median(ys), 4)
+        if not narrow:
+            res["encode_queue_slow_path"] = timed(
+                lambda: self.encode_queue(buf, dst, ej), 2)
+        return res
+
+
+def put_main(a, out):
+    if "A" in a.only:
+        out["A_put_rs63"] = PutProbe("EC6P3").run(
+            [8 * MIB] * (1024 // a.scale), reps=7, narrow=True)
+        torch.cuda.empty_cache()
+    if "B" in a.only:
+        for name in ("EC6P6", "EC15P12"):
+            out["B_put_" + name] = PutProbe(name).run(
+                [4 * MIB] * (512 // a.scale), reps=7, narrow=False)
+            torch.cuda.empty_cache()
+    if "C" in a.only:
+        rng = random.Random(7)               # the lengths of (b)
+        lens = [rng.choice([64 * KIB, MIB, 4 * MIB])
+                for _ in range(4096 // a.scale)]
+        out["C_put_mixed_EC15P12"] = PutProbe("EC15P12").run(
+            lens, reps=5, narrow=False)
+        torch.cuda.empty_cache()
+
+
 def shard_write_main(a, out):
     p = ShardWriteProbe()
     if "x" in a.only:
@@ -987,7 +1130,7 @@ def main():
                     help="which configurations to run, e.g. 'ac'; the "
                     "encode+frame queue's are 'fpghi' (p = f'), the read "
                     "queue's 'rs', the shard read queue's 'uvw', the shard "
-                    "write queue's 'xyz'")
+                    "write queue's 'xyz', the put queue's 'ABC'")
     a = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "scale": a.scale}
     if set(a.only) & set("fpghi"):
@@ -998,6 +1141,8 @@ def main():
         shard_main(a, out)
     if set(a.only) & set("xyz"):
         shard_write_main(a, out)
+    if set(a.only) & set("ABC"):
+        put_main(a, out)
     if not set(a.only) & set("abcde"):
         line = json.dumps(out)
         print(line)
